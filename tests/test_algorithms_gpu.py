@@ -132,9 +132,12 @@ class TestGPUAlgorithms:
 
     def test_bench_smoke(self):
         """One IMPALA learner step (the graft smoke path)."""
+        import os
         import sys
 
-        sys.path.insert(0, ".")
+        sys.path.insert(
+            0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        )
         from bench import ImpalaLearnerBench
 
         b = ImpalaLearnerBench(

@@ -1,5 +1,6 @@
 """Auto layer tests: config generation, validation, CLI, launch."""
 import json
+import os
 import subprocess
 import sys
 
@@ -17,6 +18,8 @@ from machin_amd.auto.config import (
     validate_config,
 )
 from machin_amd.utils.conf import Config
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def full_config(algo="DQN", env="CartPole-v1", tmpdir="/tmp/trial_auto"):
@@ -99,7 +102,7 @@ class TestCLI:
             [sys.executable, "-m", "machin_amd.auto", "generate",
              "--algo", "PPO", "--env", "CartPole-v1",
              "--output", str(out)],
-            capture_output=True, text=True, cwd="/root/repo", timeout=120,
+            capture_output=True, text=True, cwd=REPO, timeout=120,
         )
         assert r.returncode == 0, r.stderr
         data = json.loads(out.read_text())
@@ -108,7 +111,7 @@ class TestCLI:
     def test_list_cli(self):
         r = subprocess.run(
             [sys.executable, "-m", "machin_amd.auto", "list"],
-            capture_output=True, text=True, cwd="/root/repo", timeout=120,
+            capture_output=True, text=True, cwd=REPO, timeout=120,
         )
         assert r.returncode == 0
         assert "CartPole-v1" in r.stdout

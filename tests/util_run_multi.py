@@ -3,6 +3,7 @@ test/util_run_multi.py — 3 worker processes, real gloo backend, no
 cluster)."""
 import multiprocessing as mp
 import os
+import queue
 import socket
 import traceback
 
@@ -74,7 +75,22 @@ def run_multi(func, world_size: int = 3, args=(), timeout: float = 120,
     failures = {}
     try:
         for _ in range(world_size):
-            rank, ok, value = rq.get(timeout=timeout)
+            try:
+                rank, ok, value = rq.get(timeout=timeout)
+            except queue.Empty:
+                # a rank that failed early leaves its peers waiting for
+                # it: show its traceback, not just the timeout
+                report = "\n\n".join(
+                    f"Rank {r} failed:\n{v}"
+                    for r, v in sorted(failures.items())
+                )
+                silent = sorted(
+                    set(range(world_size)) - set(results) - set(failures)
+                )
+                raise AssertionError(
+                    f"ranks {silent} did not report within {timeout}s"
+                    f"\n{report}"
+                ) from None
             if ok:
                 results[rank] = value
             else:
