@@ -13,6 +13,7 @@ __all__ = [
     "DistributedBuffer",
     "DistributedPrioritizedBuffer",
     "DeviceTransitionBuffer",
+    "DeviceFrameStackBuffer",
     "default_buffer",
 ]
 
@@ -55,4 +56,8 @@ def __getattr__(name):
         from .device_buffer import DeviceTransitionBuffer
 
         return DeviceTransitionBuffer
+    if name == "DeviceFrameStackBuffer":
+        from .frame_stack_buffer import DeviceFrameStackBuffer
+
+        return DeviceFrameStackBuffer
     raise AttributeError(name)

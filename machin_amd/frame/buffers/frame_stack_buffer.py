@@ -1,0 +1,346 @@
+"""Frame-deduplicated HBM replay for frame-stacked pixel observations.
+
+No reference counterpart. :class:`.device_buffer.DeviceTransitionBuffer`
+stores each Atari-shaped transition as two full ``[4, 84, 84]`` u8
+stacks (``state`` and ``next_state``): 56 448 bytes for 7 056 bytes of
+new information, because seven of the eight planes are copies of planes
+held by neighbouring transitions. This buffer stores every frame ONCE
+in a ring of planes and rebuilds both stacks when sampling with one
+gfx950 kernel (:func:`machin_amd.ops.framestack_gather`), so the same
+HBM holds about eight times as many transitions.
+
+Layout:
+
+* frame ring ``[buffer_size, H, W]`` u8 — an episode of ``L``
+  transitions occupies ``L + k`` consecutive slots: the ``k`` planes
+  of its first state, then the newest plane of every next_state;
+* transition ring — every other column (other state keys, action,
+  reward, terminal, custom attributes) plus one int64 column holding
+  the transition's base plane slot. Transition ``t`` of an episode
+  written at slot ``s`` has base ``s + t``; its state is planes
+  ``base .. base+k-1`` and its next_state planes ``base+1 .. base+k``.
+
+Eviction is by overwritten planes. All bookkeeping is host integers
+(absolute plane / transition counters and a deque of ``(first base,
+count)`` per episode), so neither storing nor sampling waits for the
+device.
+"""
+from collections import deque
+from typing import Dict, Union
+
+import torch as t
+
+from ... import ops
+from .device_buffer import DeviceReplayBuffer, DeviceTransitionBuffer
+
+
+class DeviceFrameStackBuffer(DeviceTransitionBuffer):
+    """Device replay that stores each frame once.
+
+    Speaks the algorithm-facing API of :class:`DeviceTransitionBuffer`
+    (``store_episode`` / ``store_transition`` / ``sample_batch`` /
+    ``update_priority`` / ``size`` / ``clear``), so any algorithm takes
+    it through its ``replay_buffer=`` argument.
+
+    ``buffer_size`` is the capacity in FRAMES (ring planes), not in
+    transitions: an episode of ``L`` transitions costs ``L + k`` slots,
+    so at most ``buffer_size - k`` transitions are live. A transition
+    stored alone (``store_transition``) is an episode of length 1 and
+    costs ``k + 1`` slots — store whole episodes to get the saving.
+
+    ``state[frame_key]`` / ``next_state[frame_key]`` must be u8
+    ``[1, k, H, W]`` sliding-window stacks: within an episode
+    ``next_state_t[:k-1] == state_t[1:]`` and ``state_{t+1} ==
+    next_state_t``. With ``validate=True`` this is checked on every
+    ``store_episode`` (for frames that already live on a GPU the check
+    reads one flag back, the only host wait in this class; keep frames
+    on the host or pass ``validate=False`` to avoid it). Whatever
+    padding the environment used at reset is kept bit-for-bit because
+    the first state's ``k`` planes are stored as they are.
+
+    ``frame_layout="nhwc"`` returns the sampled stacks in
+    ``torch.channels_last`` strides (logical shape stays
+    ``[B, k, H, W]``).
+
+    Eviction: writing ring slots ``[h, h+n)`` kills exactly the
+    transitions whose base lies in that range (windows look forward and
+    never leave their own episode's slots), oldest first, so live
+    transitions stay a contiguous range of the transition ring.
+    """
+
+    def __init__(
+        self,
+        buffer_size: int,
+        device: Union[str, t.device] = "cuda:0",
+        frame_stack: int = 4,
+        frame_key: str = "state",
+        frame_layout: str = "nchw",
+        prioritized: bool = False,
+        validate: bool = True,
+        **per_kwargs,
+    ):
+        super().__init__(buffer_size, device, prioritized, **per_kwargs)
+        self.frame_stack = int(frame_stack)
+        if not 1 <= self.frame_stack <= 8:
+            raise ValueError("frame_stack must be in [1, 8].")
+        if self.buffer_size < self.frame_stack + 1:
+            raise ValueError(
+                "buffer_size (frames) must be at least frame_stack + 1."
+            )
+        if frame_layout not in ("nchw", "nhwc"):
+            raise ValueError("frame_layout must be 'nchw' or 'nhwc'.")
+        self.frame_key = frame_key
+        self.frame_layout = frame_layout
+        self.validate = validate
+        self.epsilon = self._per_kwargs["epsilon"]
+        self.alpha = self._per_kwargs["alpha"]
+        self.curr_beta = self._per_kwargs["beta"]
+        self.beta_increment_per_sampling = self._per_kwargs[
+            "beta_increment_per_sampling"
+        ]
+        self._state_col = f"state/{frame_key}"
+        self._next_col = f"next_state/{frame_key}"
+        # an episode wastes k slots, so this bounds the live count
+        self._t_capacity = self.buffer_size - self.frame_stack
+        self._planes = None  # [buffer_size, H, W] u8, first store
+        self._tree = None
+        self._max_priority = None
+        self._reset_counters()
+
+    def _reset_counters(self):
+        self._plane_count = 0  # absolute: planes ever written
+        self._t_count = 0  # absolute: transitions ever written
+        self._live = 0
+        # per episode [absolute first live base, live count], oldest first
+        self._episodes = deque()
+
+    # -- layout --------------------------------------------------------
+    def _ensure_rings(self, cols: Dict[str, t.Tensor], frame_shape):
+        if self._inner is not None:
+            return
+        dev = self.buffer_device
+        spec = {
+            k: (tuple(v.shape[1:]), v.dtype) for k, v in cols.items()
+        }
+        self._inner = DeviceReplayBuffer(self._t_capacity, spec, dev)
+        self._planes = t.empty(
+            (self.buffer_size, *frame_shape), dtype=t.uint8, device=dev
+        )
+        if self.prioritized:
+            from ...ops.sumtree import DeviceSumTree
+
+            self._tree = DeviceSumTree(self._t_capacity, dev)
+            self._max_priority = t.ones((), device=dev)
+        self._attr_order = sorted(
+            {k.split("/", 1)[0] for k in spec if k != "_base"}
+            | {"state", "next_state"}
+        )
+
+    def _check_frames(self, states: t.Tensor, nexts: t.Tensor):
+        """Sliding-window property of an episode's [L, k, H, W] stacks."""
+        bad = (nexts[:, :-1] != states[:, 1:]).flatten(1).any(1)
+        if states.shape[0] > 1:
+            bad[:-1] |= (states[1:] != nexts[:-1]).flatten(1).any(1)
+        if bool(bad.any()):
+            step = int(bad.nonzero()[0])
+            raise ValueError(
+                f"Frames of step {step} are not a sliding window: need "
+                f"next_state[:k-1] == state[1:] and the following "
+                f"state == next_state (pass validate=False to store "
+                f"anyway)."
+            )
+
+    # -- storing -------------------------------------------------------
+    def store_flat(self, batch):
+        raise NotImplementedError(
+            "DeviceFrameStackBuffer stores whole episodes "
+            "(store_episode); a flat batch has no frame order."
+        )
+
+    def store_episode(self, episode, required_attrs=("state", "action",
+                      "next_state", "reward", "terminal"), **__):
+        k = self.frame_stack
+        cols = self.flatten_episode(episode, required_attrs)
+        if self._state_col not in cols or self._next_col not in cols:
+            raise ValueError(
+                f"Transitions need state[{self.frame_key!r}] and "
+                f"next_state[{self.frame_key!r}] frame stacks."
+            )
+        states = cols.pop(self._state_col)
+        nexts = cols.pop(self._next_col)
+        for name, v in (("state", states), ("next_state", nexts)):
+            if v.dtype != t.uint8 or v.dim() != 4 or v.shape[1] != k:
+                raise ValueError(
+                    f"{name}[{self.frame_key!r}] must be a uint8 "
+                    f"[1, {k}, H, W] frame stack, got "
+                    f"{tuple(v.shape[1:])} {v.dtype}."
+                )
+        if nexts.shape != states.shape:
+            raise ValueError("state and next_state frame shapes differ.")
+        L = states.shape[0]
+        n = L + k
+        if n > self.buffer_size:
+            raise ValueError(
+                f"Episode of {L} transitions needs {n} frame slots, "
+                f"buffer_size is {self.buffer_size}."
+            )
+        if self.validate:
+            self._check_frames(states, nexts)
+        frames = t.cat([states[0], nexts[:, -1]], dim=0)
+        with self._lock:
+            F, T = self.buffer_size, self._t_capacity
+            first = self._plane_count
+            cols["_base"] = t.arange(first, first + L, dtype=t.int64) % F
+            self._ensure_rings(cols, tuple(frames.shape[1:]))
+            # refuse before any bookkeeping changes
+            if frames.shape[1:] != self._planes.shape[1:]:
+                raise ValueError("Frame size differs from the ring's.")
+            if set(cols) != set(self._inner.spec):
+                raise ValueError(
+                    f"Transition attributes {sorted(cols)} differ from "
+                    f"the stored ones {sorted(self._inner.spec)}."
+                )
+            # -- evict by overwritten planes (host integers only)
+            t_tail = self._t_count - self._live
+            horizon = first + n - F  # absolute bases below this die
+            killed = 0
+            while self._episodes and self._episodes[0][0] < horizon:
+                ep = self._episodes[0]
+                dead = min(ep[1], horizon - ep[0])
+                ep[0] += dead
+                ep[1] -= dead
+                killed += dead
+                if ep[1] == 0:
+                    self._episodes.popleft()
+            self._live -= killed
+            # -- one H2D copy per column through the pinned slabs
+            staged = self._stage({**cols, "_frames": frames})
+            frames = staged.pop("_frames").to(
+                self.buffer_device, non_blocking=True
+            )
+            h = first % F
+            if h + n <= F:
+                self._planes[h : h + n] = frames
+            else:
+                self._planes[h:] = frames[: F - h]
+                self._planes[: h + n - F] = frames[F - h :]
+            pos = self._inner.store_batch(staged)
+            if self._pinned_event is not None:
+                self._pinned_event.record()
+            if self._tree is not None:
+                # killed slots that the new transitions do not reuse
+                # get priority 0; new ones the running max priority
+                t_head = self._t_count
+                lo = max(t_tail, t_head + L - T)
+                dead_pos = t.arange(
+                    lo, max(lo, t_tail + killed),
+                    device=self.buffer_device,
+                ) % T
+                self._tree.update_leaf_batch(
+                    t.cat([
+                        t.zeros(dead_pos.numel(),
+                                device=self.buffer_device),
+                        self._max_priority.expand(L),
+                    ]),
+                    t.cat([dead_pos, pos]),
+                )
+            self._episodes.append([first, L])
+            self._plane_count += n
+            self._t_count += L
+            self._live += L
+
+    # -- sampling ------------------------------------------------------
+    def _is_live(self, pos: t.Tensor) -> t.Tensor:
+        tail = (self._t_count - self._live) % self._t_capacity
+        return (pos - tail) % self._t_capacity < self._live
+
+    def _uniform_live(self, batch_size: int) -> t.Tensor:
+        tail = self._t_count - self._live
+        return (
+            t.randint(0, self._live, (batch_size,),
+                      device=self.buffer_device) + tail
+        ) % self._t_capacity
+
+    def sample_batch(
+        self,
+        batch_size: int,
+        concatenate: bool = True,
+        device=None,
+        sample_method=None,
+        sample_attrs=None,
+        additional_concat_custom_attrs=None,
+        *_,
+        **__,
+    ):
+        if not concatenate:
+            raise ValueError(
+                "DeviceFrameStackBuffer only supports concatenated "
+                "sampling (flat device rings)."
+            )
+        with self._lock:
+            if self._live == 0 or batch_size <= 0:
+                return (0, None, None, None) if self.prioritized \
+                    else (0, None)
+            is_weight = None
+            if self.prioritized:
+                pos = self._tree.sample(batch_size, stratified=True)
+                # the float edge of the stratified search can land on
+                # a zero-priority (dead) leaf: swap in a live one
+                pos = t.where(
+                    self._is_live(pos), pos,
+                    self._uniform_live(batch_size),
+                )
+                leaf_w = self._tree.get_leaf_weight(pos)
+                total = self._tree.get_weight_sum_tensor()
+                probs = (leaf_w / total).clamp_min(1e-12)
+                is_weight = (self._live * probs) ** (-self.curr_beta)
+                is_weight = is_weight / is_weight.max()
+                self.curr_beta = min(
+                    1.0,
+                    self.curr_beta + self.beta_increment_per_sampling,
+                )
+            else:
+                pos = self._uniform_live(batch_size)
+            cols = self._inner.gather(pos)
+            state, next_state = ops.framestack_gather(
+                self._planes, cols.pop("_base"), self.frame_stack,
+                channels_last=self.frame_layout == "nhwc",
+            )
+            cols[self._state_col] = state
+            cols[self._next_col] = next_state
+            attrs = sample_attrs or (self._attr_order + ["*"])
+            batch = self._structure(cols, attrs)
+            if self.prioritized:
+                return batch_size, batch, pos, is_weight
+            return batch_size, batch
+
+    # -- PER interface -------------------------------------------------
+    def update_priority(self, priorities, indexes):
+        if self._tree is None:
+            raise RuntimeError("Buffer is not prioritized (or empty).")
+        dev = self.buffer_device
+        with self._lock:
+            prio = t.as_tensor(priorities, dtype=t.float32).to(dev)
+            pos = t.as_tensor(indexes).to(dev).long().view(-1)
+            prio = (prio.view(-1).abs() + self.epsilon) ** self.alpha
+            # a slot evicted since it was sampled stays at priority 0
+            prio = t.where(self._is_live(pos), prio, t.zeros_like(prio))
+            self._max_priority = t.maximum(
+                self._max_priority, prio.max()
+            )
+            self._tree.update_leaf_batch(prio, pos)
+
+    # -- bookkeeping ---------------------------------------------------
+    def size(self) -> int:
+        """Number of live transitions."""
+        return self._live
+
+    def clear(self):
+        with self._lock:
+            self._reset_counters()
+            self.curr_beta = self._per_kwargs["beta"]
+            if self._inner is not None:
+                self._inner.clear()
+            if self._tree is not None:
+                self._tree.weights.zero_()
+                self._max_priority = t.ones((), device=self.buffer_device)

@@ -530,9 +530,67 @@ def dequant_u8(frames: t.Tensor, scale: float = 1.0 / 255.0) -> t.Tensor:
     return frames.to(t.bfloat16) * scale
 
 
+def _framestack_gather_torch(
+    planes: t.Tensor, base: t.Tensor, k: int, channels_last: bool
+):
+    """Torch composition of :func:`framestack_gather` (the CPU path
+    and the reference the kernel is tested and timed against)."""
+    P = planes.shape[0]
+    # modular index matrix [B, k+1]; python-style % is non-negative
+    idx = (
+        base.long().view(-1, 1)
+        + t.arange(k + 1, device=base.device).view(1, -1)
+    ) % P
+    win = planes.index_select(0, idx.view(-1)).view(
+        -1, k + 1, *planes.shape[1:]
+    )
+    fmt = t.channels_last if channels_last else t.contiguous_format
+    return (
+        win[:, :k].contiguous(memory_format=fmt),
+        win[:, 1:].contiguous(memory_format=fmt),
+    )
+
+
+def framestack_gather(
+    planes: t.Tensor, base: t.Tensor, k: int, channels_last: bool = False
+):
+    """Rebuild ``(state, next_state)`` frame stacks from a ring of
+    frames stored once (frame-deduplicated replay).
+
+    ``planes`` is the u8 ring ``[P, H, W]``, ``base`` int64 ``[B]``.
+    Window plane ``j`` (``0 <= j <= k``) of sample ``b`` is ring slot
+    ``(base[b] + j) mod P`` (non-negative modulo, so the window may
+    wrap and no value of ``base`` addresses outside the ring);
+    ``state[b, j]`` is plane ``j`` for ``j < k`` and
+    ``next_state[b, j-1]`` is plane ``j`` for ``j >= 1``. Both outputs
+    are u8 ``[B, k, H, W]``, plain contiguous or, with
+    ``channels_last=True``, in ``torch.channels_last`` strides (memory
+    ``[B, H, W, k]``, what the fused u8 conv stem consumes).
+
+    On ROCm one gfx950 kernel loads each plane once per sample and
+    writes both stacks (machin_amd/ops/hip/framestack.hip); the CPU
+    fallback is the same semantics as a torch composition.
+    """
+    k = int(k)
+    if planes.is_cuda:
+        ext = _require_ext()
+        state, next_state = ext.framestack_gather(
+            planes, base, k, bool(channels_last)
+        )
+        return state, next_state
+    if planes.dim() != 3 or planes.dtype != t.uint8:
+        raise ValueError("planes must be a uint8 [P, H, W] ring")
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in [1, 8]")
+    if planes.shape[0] < k + 1:
+        raise ValueError("ring needs at least k+1 planes")
+    return _framestack_gather_torch(planes, base, k, bool(channels_last))
+
+
 __all__ = [
     "available",
     "dequant_u8",
+    "framestack_gather",
     "polyak_update_",
     "discounted_returns",
     "gae",

@@ -50,6 +50,9 @@ void ou_update_launch(float*, int64_t, float, float, float, float, uint64_t,
                       uint64_t, hipStream_t);
 void u8_to_bf16_scale_launch(const unsigned char*, void*, int64_t, float,
                              hipStream_t);
+void framestack_gather_launch(const unsigned char*, const int64_t*,
+                              unsigned char*, unsigned char*, int64_t,
+                              int64_t, int64_t, int, bool, hipStream_t);
 void pg_head_fwd_launch(const void*, const int64_t*, float*, float*,
                         int64_t, int, hipStream_t);
 void pg_head_bwd_launch(const void*, const int64_t*, const float*,
@@ -364,6 +367,38 @@ Tensor u8_to_bf16_scale(Tensor in, double scale) {
   return out;
 }
 
+// frame-deduplicated replay: rebuild (state, next_state) stacks
+// [B, k, H, W] from a ring of u8 planes [P, H, W]; window plane j of
+// sample b is ring slot (base[b] + j) mod P. The kernel reduces base
+// modulo P itself, so values are never inspected on the host.
+std::vector<Tensor> framestack_gather(Tensor planes, Tensor base, int64_t k,
+                                      bool channels_last) {
+  TORCH_CHECK(planes.is_cuda() && planes.scalar_type() == at::kByte &&
+                  planes.is_contiguous(),
+              "planes must be contiguous uint8 CUDA");
+  TORCH_CHECK(planes.dim() == 3, "planes must be [P, H, W]");
+  TORCH_CHECK(base.is_cuda() && base.scalar_type() == at::kLong &&
+                  base.is_contiguous() && base.dim() == 1,
+              "base must be contiguous 1-D int64 CUDA");
+  TORCH_CHECK(base.device() == planes.device(),
+              "planes and base must be on the same device");
+  TORCH_CHECK(k >= 1 && k <= 8, "k must be in [1, 8]");
+  const int64_t P = planes.size(0), H = planes.size(1), W = planes.size(2);
+  TORCH_CHECK(P >= k + 1, "ring needs at least k+1 planes");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(planes.device());
+  const int64_t B = base.numel();
+  const auto fmt = channels_last ? at::MemoryFormat::ChannelsLast
+                                 : at::MemoryFormat::Contiguous;
+  Tensor state = at::empty({B, k, H, W}, planes.options(), fmt);
+  Tensor next = at::empty({B, k, H, W}, planes.options(), fmt);
+  framestack_gather_launch(planes.data_ptr<unsigned char>(),
+                           base.data_ptr<int64_t>(),
+                           state.data_ptr<unsigned char>(),
+                           next.data_ptr<unsigned char>(), B, P, H * W,
+                           (int)k, channels_last, current_stream());
+  return {state, next};
+}
+
 std::vector<Tensor> conv1_wrw(Tensor dy, Tensor frames, double scale) {
   // dy: [K, 32] bf16 (NHWC-flattened conv output grad);
   // frames: [B, 84, 84, 4] u8. Returns [32, 4, 8, 8] fp32 grad.
@@ -478,6 +513,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("normal_noise_", &normal_noise_);
   m.def("ou_update_", &ou_update_);
   m.def("u8_to_bf16_scale", &u8_to_bf16_scale);
+  m.def("framestack_gather", &framestack_gather);
   m.def("pg_head_fwd", &pg_head_fwd);
   m.def("pg_head_bwd", &pg_head_bwd);
   m.def("conv1_wrw", &conv1_wrw);

@@ -1,0 +1,201 @@
+// gfx950 frame-stack gather for frame-deduplicated replay.
+//
+// The replay stores every frame ONCE in a ring of u8 planes [P, H, W].
+// A sampled transition b owns the k+1 consecutive ring slots
+// (base[b] + j) mod P, j = 0..k: planes 0..k-1 are its state stack,
+// planes 1..k its next_state stack. This kernel rebuilds both stacks
+// in one pass: each plane is loaded once per sample and stored to its
+// one or two destinations (k+1 plane reads + 2k plane writes per
+// sample; the torch composition index_select -> two slices ->
+// two layout copies moves about twice that in 4-5 launches).
+//
+// Pure byte movement, memory-bound (guide §6 G13: 16 B/lane):
+// - vector path (H*W % 16 == 0, 16 B aligned ring): one work item =
+//   16 pixels of one sample, k+1 dwordx4 loads;
+//     NCHW: each loaded plane chunk goes out as dwordx4 stores;
+//     NHWC, k == 4: the 4x16 bytes are transposed in registers with
+//     v_perm_b32 and leave as four dwordx4 stores per stack.
+// - scalar path (any other H*W, other k in NHWC): one work item = one
+//   pixel of one sample.
+// No LDS, no atomics. `base` is reduced into [0, P) in the kernel
+// (non-negative modulo), so no int64 value can address outside the
+// ring and the host never has to look at the values.
+#include "common.h"
+
+typedef unsigned char u8;
+typedef uint32_t u32;
+
+#define FS_MAX_K 8
+
+// ring slot of window plane j: s in [0, P), j <= k < P  ->  s + j < 2P
+__device__ __forceinline__ int64_t fs_slot(int64_t s, int j, int64_t P) {
+  int64_t r = s + j;
+  return r >= P ? r - P : r;
+}
+
+__device__ __forceinline__ int64_t fs_base(const int64_t* __restrict__ base,
+                                           int64_t b, int64_t P) {
+  int64_t s = base[b] % P;
+  return s < 0 ? s + P : s;
+}
+
+// ---------------------------------------------------------------------
+// NCHW vector path. C = H*W/16 chunks per plane; out index of chunk c
+// of channel j of sample b is (b*K + j)*C + c.
+// ---------------------------------------------------------------------
+template <int K>
+__global__ void framestack_nchw_vec_kernel(const uint4* __restrict__ planes,
+                                           const int64_t* __restrict__ base,
+                                           uint4* __restrict__ state,
+                                           uint4* __restrict__ next,
+                                           int64_t B, int64_t P, int64_t C) {
+  const int64_t total = B * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / C, c = i - b * C;
+    const int64_t s = fs_base(base, b, P);
+    uint4 v[K + 1];
+#pragma unroll
+    for (int j = 0; j <= K; ++j) v[j] = planes[fs_slot(s, j, P) * C + c];
+    const int64_t o = b * K * C + c;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      state[o + j * C] = v[j];
+      next[o + j * C] = v[j + 1];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------
+// NHWC k == 4 vector path: 4x4 byte transposes with v_perm_b32.
+// __builtin_amdgcn_perm(hi, lo, sel): result byte n = byte sel[n] of
+// the 8-byte value {hi, lo} (selectors 0-3 -> lo, 4-7 -> hi).
+// ---------------------------------------------------------------------
+// words a,b,c,d hold 4 pixels of channels 0..3; o[q] = pixel q's
+// 4 channel bytes (a_q, b_q, c_q, d_q).
+__device__ __forceinline__ void fs_transpose4(u32 a, u32 b, u32 c, u32 d,
+                                              u32 o[4]) {
+  u32 ab_lo = __builtin_amdgcn_perm(b, a, 0x05010400u);  // a0 b0 a1 b1
+  u32 ab_hi = __builtin_amdgcn_perm(b, a, 0x07030602u);  // a2 b2 a3 b3
+  u32 cd_lo = __builtin_amdgcn_perm(d, c, 0x05010400u);  // c0 d0 c1 d1
+  u32 cd_hi = __builtin_amdgcn_perm(d, c, 0x07030602u);  // c2 d2 c3 d3
+  o[0] = __builtin_amdgcn_perm(cd_lo, ab_lo, 0x05040100u);
+  o[1] = __builtin_amdgcn_perm(cd_lo, ab_lo, 0x07060302u);
+  o[2] = __builtin_amdgcn_perm(cd_hi, ab_hi, 0x05040100u);
+  o[3] = __builtin_amdgcn_perm(cd_hi, ab_hi, 0x07060302u);
+}
+
+__device__ __forceinline__ u32 fs_word(const uint4& v, int g) {
+  return g == 0 ? v.x : g == 1 ? v.y : g == 2 ? v.z : v.w;
+}
+
+// 16 pixels x 4 channels -> 64 interleaved bytes = 4 dwordx4 stores
+__device__ __forceinline__ void fs_store_nhwc4(uint4* __restrict__ dst,
+                                               const uint4& p0,
+                                               const uint4& p1,
+                                               const uint4& p2,
+                                               const uint4& p3) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    u32 o[4];
+    fs_transpose4(fs_word(p0, g), fs_word(p1, g), fs_word(p2, g),
+                  fs_word(p3, g), o);
+    dst[g] = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+__global__ void framestack_nhwc4_vec_kernel(const uint4* __restrict__ planes,
+                                            const int64_t* __restrict__ base,
+                                            uint4* __restrict__ state,
+                                            uint4* __restrict__ next,
+                                            int64_t B, int64_t P,
+                                            int64_t C) {
+  const int64_t total = B * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / C, c = i - b * C;
+    const int64_t s = fs_base(base, b, P);
+    uint4 v[5];
+#pragma unroll
+    for (int j = 0; j <= 4; ++j) v[j] = planes[fs_slot(s, j, P) * C + c];
+    // sample b holds C*4 uint4 per stack; item i owns uint4 [4i, 4i+4)
+    fs_store_nhwc4(state + 4 * i, v[0], v[1], v[2], v[3]);
+    fs_store_nhwc4(next + 4 * i, v[1], v[2], v[3], v[4]);
+  }
+}
+
+// ---------------------------------------------------------------------
+// scalar path: one work item = one pixel of one sample, any H*W, any
+// k <= FS_MAX_K, both layouts.
+// ---------------------------------------------------------------------
+__global__ void framestack_scalar_kernel(const u8* __restrict__ planes,
+                                         const int64_t* __restrict__ base,
+                                         u8* __restrict__ state,
+                                         u8* __restrict__ next, int64_t B,
+                                         int64_t P, int64_t HW, int k,
+                                         bool nhwc) {
+  const int64_t total = B * HW;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / HW, px = i - b * HW;
+    const int64_t s = fs_base(base, b, P);
+    // element (b, j, px): NCHW (b*k + j)*HW + px, NHWC (b*HW + px)*k + j
+    const int64_t o = nhwc ? i * k : b * k * HW + px;
+    const int64_t step = nhwc ? 1 : HW;
+    for (int j = 0; j <= k; ++j) {
+      u8 v = planes[fs_slot(s, j, P) * HW + px];
+      if (j < k) state[o + j * step] = v;
+      if (j >= 1) next[o + (j - 1) * step] = v;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------
+// host-side driver (called from bindings.cpp)
+// ---------------------------------------------------------------------
+template <int K>
+static void fs_launch_nchw_vec(const u8* planes, const int64_t* base,
+                               u8* state, u8* next, int64_t B, int64_t P,
+                               int64_t C, hipStream_t stream) {
+  const int block = 256;
+  hipLaunchKernelGGL(framestack_nchw_vec_kernel<K>,
+                     dim3(ma_grid(B * C, block)), dim3(block), 0, stream,
+                     (const uint4*)planes, base, (uint4*)state,
+                     (uint4*)next, B, P, C);
+}
+
+void framestack_gather_launch(const unsigned char* planes,
+                              const int64_t* base, unsigned char* state,
+                              unsigned char* next, int64_t B, int64_t P,
+                              int64_t HW, int k, bool nhwc,
+                              hipStream_t stream) {
+  if (B == 0 || HW == 0) return;
+  const int block = 256;
+  const bool aligned =
+      (((uintptr_t)planes | (uintptr_t)state | (uintptr_t)next) & 15) == 0;
+  const bool vec = (HW % 16 == 0) && aligned;
+  const int64_t C = HW / 16;
+  if (vec && !nhwc) {
+    switch (k) {
+      case 1: fs_launch_nchw_vec<1>(planes, base, state, next, B, P, C, stream); return;
+      case 2: fs_launch_nchw_vec<2>(planes, base, state, next, B, P, C, stream); return;
+      case 3: fs_launch_nchw_vec<3>(planes, base, state, next, B, P, C, stream); return;
+      case 4: fs_launch_nchw_vec<4>(planes, base, state, next, B, P, C, stream); return;
+      case 5: fs_launch_nchw_vec<5>(planes, base, state, next, B, P, C, stream); return;
+      case 6: fs_launch_nchw_vec<6>(planes, base, state, next, B, P, C, stream); return;
+      case 7: fs_launch_nchw_vec<7>(planes, base, state, next, B, P, C, stream); return;
+      case 8: fs_launch_nchw_vec<8>(planes, base, state, next, B, P, C, stream); return;
+      default: break;
+    }
+  }
+  if (vec && nhwc && k == 4) {
+    hipLaunchKernelGGL(framestack_nhwc4_vec_kernel,
+                       dim3(ma_grid(B * C, block)), dim3(block), 0, stream,
+                       (const uint4*)planes, base, (uint4*)state,
+                       (uint4*)next, B, P, C);
+    return;
+  }
+  hipLaunchKernelGGL(framestack_scalar_kernel,
+                     dim3(ma_grid(B * HW, block)), dim3(block), 0, stream,
+                     planes, base, state, next, B, P, HW, k, nhwc);
+}

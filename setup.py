@@ -27,6 +27,7 @@ SOURCES = [
     "multi_tensor.hip",
     "distributions.hip",
     "elementwise.hip",
+    "framestack.hip",
     "conv1_wrw.hip",
 ]
 

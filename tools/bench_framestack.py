@@ -1,0 +1,167 @@
+"""Time the frame-stack gather of the frame-deduplicated replay.
+
+    python tools/bench_framestack.py [--out table.md]
+
+For 84x84 frames, k=4 and B in {32, 512, 4096}, in both output
+layouts, three ways of producing one sampled (state, next_state)
+batch are timed on the GPU:
+
+* kernel   — ``ops.framestack_gather`` (one gfx950 kernel);
+* torch    — the same result as a torch composition over the SAME
+             frame ring (index matrix, ``index_select``, two slices,
+             two layout copies);
+* stacked  — what ``DeviceTransitionBuffer`` does: ``index_select``
+             from two pre-stacked ``[N, 4, 84, 84]`` rings (for the
+             NHWC rows plus the two ``channels_last`` copies needed
+             to hand the batch to the fused u8 conv stem).
+
+Method: all three are checked to return the same bytes first; then
+each is warmed up and timed with device events over ``--iters`` calls,
+``--rounds`` times, alternating the three variants inside a round; the
+median round is reported with the min-max spread. Indices are fresh
+random draws per call from a ring larger than the 256 MiB Infinity
+Cache, as in a real replay. Needs a GPU; there is no CPU mode.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(
+    0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+)
+
+import torch as t
+
+from machin_amd import ops
+
+H = W = 84
+K = 4
+
+
+def stored_bytes(episode_len: int):
+    """Bytes of HBM per stored transition for the frame columns (plus
+    the int64 base-slot column of the frame ring)."""
+    stacked = 2 * K * H * W
+    dedup = H * W * (episode_len + K) / episode_len + 8
+    return stacked, dedup
+
+
+def time_ms(fn, draws, iters):
+    start = t.cuda.Event(enable_timing=True)
+    stop = t.cuda.Event(enable_timing=True)
+    start.record()
+    for i in range(iters):
+        fn(draws[i % len(draws)])
+    stop.record()
+    stop.synchronize()
+    return start.elapsed_time(stop) / iters
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--frames", type=int, default=65536,
+                        help="planes in the frame ring (462 MB)")
+    parser.add_argument("--transitions", type=int, default=16384,
+                        help="rows of each pre-stacked ring (462 MB)")
+    parser.add_argument("--iters", type=int, default=1000)
+    parser.add_argument("--rounds", type=int, default=7)
+    parser.add_argument("--out", default=None)
+    args = parser.parse_args()
+    if not t.cuda.is_available():
+        raise SystemExit("bench_framestack needs a GPU")
+    dev = t.device("cuda:0")
+    t.manual_seed(0)
+
+    P, N = args.frames, args.transitions
+    ring = t.randint(0, 256, (P, H, W), dtype=t.uint8, device=dev)
+    # pre-stacked rings holding the same windows for bases 0..N-1
+    all_base = t.arange(N, device=dev)
+    st_ring = t.empty((N, K, H, W), dtype=t.uint8, device=dev)
+    nx_ring = t.empty_like(st_ring)
+    for lo in range(0, N, 2048):
+        s, n = ops.framestack_gather(ring, all_base[lo : lo + 2048], K)
+        st_ring[lo : lo + 2048], nx_ring[lo : lo + 2048] = s, n
+
+    rows = []
+    for nhwc in (False, True):
+        fmt = t.channels_last if nhwc else t.contiguous_format
+
+        def kernel(base):
+            return ops.framestack_gather(ring, base, K, nhwc)
+
+        def torch_same_ring(base):
+            return ops._framestack_gather_torch(ring, base, K, nhwc)
+
+        def stacked(base):
+            return (
+                st_ring.index_select(0, base).contiguous(
+                    memory_format=fmt),
+                nx_ring.index_select(0, base).contiguous(
+                    memory_format=fmt),
+            )
+
+        variants = [("kernel", kernel), ("torch", torch_same_ring),
+                    ("stacked", stacked)]
+        for B in (32, 512, 4096):
+            draws = [t.randint(0, N, (B,), device=dev) for _ in range(16)]
+            want = kernel(draws[0])
+            for _, fn in variants[1:]:
+                got = fn(draws[0])
+                assert t.equal(got[0], want[0]) and got[0].stride() == \
+                    want[0].stride()
+                assert t.equal(got[1], want[1])
+            for _, fn in variants:
+                time_ms(fn, draws, 20)  # warm-up
+            samples = {name: [] for name, _ in variants}
+            for _ in range(args.rounds):
+                for name, fn in variants:
+                    samples[name].append(time_ms(fn, draws, args.iters))
+            row = {"layout": "nhwc" if nhwc else "nchw", "B": B}
+            for name, vals in samples.items():
+                row[name + "_ms"] = statistics.median(vals)
+                row[name + "_min_ms"] = min(vals)
+                row[name + "_max_ms"] = max(vals)
+            # bytes the kernel must move: k+1 plane reads, 2k writes
+            row["kernel_GBps"] = (
+                B * (3 * K + 1) * H * W / (row["kernel_ms"] * 1e-3) / 1e9
+            )
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+
+    lines = [
+        "| layout | B | kernel ms (min-max) | torch, same ring ms | "
+        "stacked rings ms | kernel GB/s | torch / kernel | "
+        "stacked / kernel |",
+        "|---|---|---|---|---|---|---|---|",
+    ]
+    for r in rows:
+        lines.append(
+            f"| {r['layout']} | {r['B']} | {r['kernel_ms']:.4f} "
+            f"({r['kernel_min_ms']:.4f}-{r['kernel_max_ms']:.4f}) | "
+            f"{r['torch_ms']:.4f} "
+            f"({r['torch_min_ms']:.4f}-{r['torch_max_ms']:.4f}) | "
+            f"{r['stacked_ms']:.4f} "
+            f"({r['stacked_min_ms']:.4f}-{r['stacked_max_ms']:.4f}) | "
+            f"{r['kernel_GBps']:.0f} | "
+            f"{r['torch_ms'] / r['kernel_ms']:.2f}x | "
+            f"{r['stacked_ms'] / r['kernel_ms']:.2f}x |"
+        )
+    lines.append("")
+    for L in (100, 1000):
+        stacked_b, dedup_b = stored_bytes(L)
+        lines.append(
+            f"Frame bytes per stored transition, episodes of {L} steps: "
+            f"stacked {stacked_b}, frame ring {dedup_b:.0f} "
+            f"({stacked_b / dedup_b:.2f}x)."
+        )
+    table = "\n".join(lines)
+    print(table)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(table + "\n")
+
+
+if __name__ == "__main__":
+    main()
