@@ -69,21 +69,34 @@ def mlp(sizes: Sequence[int], activation=nn.ReLU, output_activation=None):
 
 
 class FusedActorCriticCNN(NeuralNetworkModule):
-    """ActorCriticCNN variant consuming RAW uint8 frames: the stem is
-    machin_amd.ops.fused_conv.FusedAtariConv1 (fused u8 dequant +
-    conv, hand-written gfx950 weight-gradient kernel); the rest of the
-    stack is identical to ActorCriticCNN."""
+    """ActorCriticCNN variant consuming RAW uint8 frames, with every
+    conv activation fused into a neighbouring kernel.
+
+    The stem is machin_amd.ops.fused_conv.FusedAtariConv1 with
+    ``relu=True`` (fused u8 dequant + conv + bias + ReLU in one
+    hand-written gfx950 kernel; the ReLU's backward is folded into the
+    weight-gradient kernel through a packed sign mask, one int32 per
+    output pixel, so the un-activated tensor is never materialised).
+    conv2 and conv3 are ConvBiasReLU2d: MIOpen conv without bias, then
+    one in-place bias+ReLU kernel forward and one ReLU-mask +
+    deterministic bias-gradient kernel backward; conv3 writes its
+    activation already flattened for the fc layer. Results are
+    bit-identical to ActorCriticCNN's conv + ReLU composition under
+    bf16 autocast; parameter names are the same (the ``nn.Identity``
+    entries keep the ``Sequential`` indices of the former ReLUs)."""
 
     def __init__(self, action_num: int = 6, feature_dim: int = 512):
         super().__init__()
-        from ...ops.fused_conv import FusedAtariConv1
+        from ...ops.fused_conv import ConvBiasReLU2d, FusedAtariConv1
 
-        self.stem = FusedAtariConv1()
+        self.stem = FusedAtariConv1(relu=True)
         self.conv_rest = nn.Sequential(
-            nn.Conv2d(32, 64, 4, stride=2),
-            nn.ReLU(inplace=True),
-            nn.Conv2d(64, 64, 3, stride=1),
-            nn.ReLU(inplace=True),
+            ConvBiasReLU2d(32, 64, 4, stride=2),
+            nn.Identity(),
+            # hands the fc its [N, 3136] input directly: no layout
+            # copy around the (now no-op) Flatten below
+            ConvBiasReLU2d(64, 64, 3, stride=1, flatten=True),
+            nn.Identity(),
         )
         self.fc = nn.Sequential(
             nn.Flatten(), nn.Linear(64 * 7 * 7, feature_dim),
@@ -93,7 +106,7 @@ class FusedActorCriticCNN(NeuralNetworkModule):
         self.value = nn.Linear(feature_dim, 1)
 
     def forward(self, frames_u8: t.Tensor):
-        x = t.relu(self.stem(frames_u8))
+        x = self.stem(frames_u8)  # already activated
         with t.autocast(device_type="cuda", dtype=t.bfloat16):
             feat = self.fc(self.conv_rest(x))
             return self.policy(feat), self.value(feat)

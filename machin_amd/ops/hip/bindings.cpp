@@ -65,6 +65,21 @@ void fwd_bfrag_probe_launch(float*, int, hipStream_t);
 void tr16_diag_launch(float*, int, hipStream_t);
 void conv1_fwd_launch(const unsigned char*, const void*, const float*,
                       void*, int64_t, float, hipStream_t);
+void conv1_fwd_relu_launch(const unsigned char*, const void*, const float*,
+                           void*, unsigned int*, int64_t, float,
+                           hipStream_t);
+void conv1_wrw_masked_launch(const void*, const unsigned int*,
+                             const unsigned char*, float*, float*, float*,
+                             int64_t, float, hipStream_t);
+void bias_relu_launch(void*, const float*, int64_t, int, hipStream_t);
+int64_t bias_relu_bwd_blocks(int64_t, int);
+void bias_relu_bwd_launch(const void*, const void*, void*, float*, float*,
+                          int64_t, int, hipStream_t);
+int64_t bias_relu_flat_blocks(int64_t);
+void bias_relu_flat_launch(const void*, const float*, void*, int64_t, int,
+                           int, hipStream_t);
+void bias_relu_flat_bwd_launch(const void*, const void*, void*, float*,
+                               float*, int64_t, int, int, hipStream_t);
 
 namespace {
 
@@ -450,6 +465,171 @@ Tensor conv1_fwd(Tensor frames, Tensor weight, Tensor bias,
   return out;
 }
 
+// Fused-activation stem forward: returns {relu(conv + bias) as [K, 32]
+// bf16, sign mask [K] int32 (bit c of word k set <=> y[k][c] > 0)}.
+std::vector<Tensor> conv1_fwd_relu(Tensor frames, Tensor weight,
+                                   Tensor bias, double scale) {
+  TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte &&
+                  frames.is_contiguous(),
+              "frames must be contiguous u8 CUDA");
+  TORCH_CHECK(weight.is_cuda() && weight.scalar_type() == at::kBFloat16 &&
+                  weight.is_contiguous() && weight.size(0) == 256 &&
+                  weight.size(1) == 32,
+              "weight must be contiguous [256,32] bf16 CUDA");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(frames.device());
+  int64_t K = frames.size(0) * 400;
+  Tensor out = at::empty({K, 32},
+                         weight.options().dtype(at::kBFloat16));
+  Tensor mask = at::empty({K}, weight.options().dtype(at::kInt));
+  const float* bias_ptr = nullptr;
+  if (bias.defined() && bias.numel() == 32) {
+    TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kFloat &&
+                    bias.is_contiguous(),
+                "bias must be contiguous fp32 CUDA");
+    bias_ptr = bias.data_ptr<float>();
+  }
+  conv1_fwd_relu_launch(frames.data_ptr<unsigned char>(),
+                        weight.data_ptr(), bias_ptr, out.data_ptr(),
+                        (unsigned int*)mask.data_ptr<int>(), K,
+                        (float)scale, current_stream());
+  return {out, mask};
+}
+
+// Weight/bias gradient of the fused-activation stem: dy is the
+// gradient w.r.t. the ACTIVATED output; elements whose mask bit is
+// clear are zeroed as they are loaded.
+std::vector<Tensor> conv1_wrw_masked(Tensor dy, Tensor mask, Tensor frames,
+                                     double scale) {
+  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
+                  dy.is_contiguous() && dy.dim() == 2 && dy.size(1) == 32,
+              "dy must be contiguous [K,32] bf16 CUDA");
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == at::kInt &&
+                  mask.is_contiguous() && mask.dim() == 1 &&
+                  mask.size(0) == dy.size(0),
+              "mask must be contiguous [K] int32 CUDA");
+  TORCH_CHECK((uintptr_t)mask.data_ptr() % 16 == 0,
+              "mask must be 16-byte aligned");
+  TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte &&
+                  frames.is_contiguous(),
+              "frames must be contiguous u8 CUDA");
+  TORCH_CHECK(dy.size(0) == frames.size(0) * 400,
+              "K must equal batch*400");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
+  Tensor scratch = at::empty({32 * 256},
+                             dy.options().dtype(at::kFloat));
+  Tensor grad_w = at::empty({32, 4, 8, 8},
+                            dy.options().dtype(at::kFloat));
+  Tensor grad_b = at::empty({32}, dy.options().dtype(at::kFloat));
+  conv1_wrw_masked_launch(dy.data_ptr(),
+                          (const unsigned int*)mask.data_ptr<int>(),
+                          frames.data_ptr<unsigned char>(),
+                          scratch.data_ptr<float>(),
+                          grad_w.data_ptr<float>(),
+                          grad_b.data_ptr<float>(), dy.size(0),
+                          (float)scale, current_stream());
+  return {grad_w, grad_b};
+}
+
+void check_rows_bf16(const Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+                  t.dim() == 2 && t.is_contiguous(),
+              name, " must be a contiguous [R, C] bf16 CUDA tensor");
+  TORCH_CHECK(t.size(1) % 8 == 0 && t.size(1) >= 8 && t.size(1) <= 2048,
+              name, ": C must be a multiple of 8 in [8, 2048]");
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, name,
+              " must be 16-byte aligned");
+}
+
+// In place on the NHWC [R, C] view of a channels-last activation:
+// y = relu(bf16(y + bf16(bias[c]))).
+void bias_relu_(Tensor y, Tensor bias) {
+  check_rows_bf16(y, "y");
+  check_f32_cuda(bias, "bias");
+  TORCH_CHECK(bias.numel() == y.size(1), "bias must have C elements");
+  TORCH_CHECK((uintptr_t)bias.data_ptr() % 16 == 0,
+              "bias must be 16-byte aligned");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  bias_relu_launch(y.data_ptr(), bias.data_ptr<float>(), y.size(0),
+                   (int)y.size(1), current_stream());
+}
+
+// {gx = y > 0 ? gy : 0 as [R, C] bf16, per-channel sum of gx rounded to
+// bf16 and returned as fp32 [C]}; the sum is deterministic.
+std::vector<Tensor> bias_relu_bwd(Tensor gy, Tensor y) {
+  check_rows_bf16(gy, "gy");
+  check_rows_bf16(y, "y");
+  TORCH_CHECK(gy.sizes() == y.sizes(), "gy and y must have equal shapes");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(gy.device());
+  const int64_t R = gy.size(0);
+  const int C = (int)gy.size(1);
+  Tensor gx = at::empty_like(gy);
+  Tensor partial = at::empty({bias_relu_bwd_blocks(R, C), C},
+                             gy.options().dtype(at::kFloat));
+  Tensor grad_bias = at::empty({C}, gy.options().dtype(at::kFloat));
+  bias_relu_bwd_launch(gy.data_ptr(), y.data_ptr(), gx.data_ptr(),
+                       partial.data_ptr<float>(),
+                       grad_bias.data_ptr<float>(), R, C,
+                       current_stream());
+  return {gx, grad_bias};
+}
+
+void check_flat_bf16(const Tensor& t, int64_t N, int64_t C, int64_t HW,
+                     const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+                  t.is_contiguous() && t.numel() == N * C * HW,
+              name, " must be a contiguous bf16 CUDA tensor of N*C*HW");
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= 2048 && HW >= 1 &&
+                  C * HW <= 32768,
+              name, ": C must be a multiple of 8 in [8, 2048] and one "
+              "sample (C*HW bf16) must fit 64 KB of LDS");
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, name,
+              " must be 16-byte aligned");
+}
+
+// relu(bf16(y + bf16(bias[c]))) of the NHWC rows y [N*HW, C], written
+// as the NCHW-flat matrix [N, C*HW] (what nn.Flatten makes of the
+// channels-last activation).
+Tensor bias_relu_flat(Tensor y, Tensor bias, int64_t N) {
+  check_rows_bf16(y, "y");
+  TORCH_CHECK(N > 0 && y.size(0) % N == 0, "rows must be N*HW");
+  const int64_t C = y.size(1), HW = y.size(0) / N;
+  check_flat_bf16(y, N, C, HW, "y");
+  check_f32_cuda(bias, "bias");
+  TORCH_CHECK(bias.numel() == C, "bias must have C elements");
+  TORCH_CHECK((uintptr_t)bias.data_ptr() % 16 == 0,
+              "bias must be 16-byte aligned");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  Tensor out = at::empty({N, C * HW}, y.options());
+  bias_relu_flat_launch(y.data_ptr(), bias.data_ptr<float>(),
+                        out.data_ptr(), N, (int)C, (int)HW,
+                        current_stream());
+  return out;
+}
+
+// Backward of bias_relu_flat: gy and the saved activation y are both
+// NCHW-flat [N, C*HW]; returns {gx as NHWC rows [N*HW, C], bias
+// gradient (deterministic, bf16-rounded) as fp32 [C]}.
+std::vector<Tensor> bias_relu_flat_bwd(Tensor gy, Tensor y, int64_t C) {
+  TORCH_CHECK(gy.dim() == 2 && y.dim() == 2 && gy.sizes() == y.sizes(),
+              "gy and y must be [N, C*HW] of equal shape");
+  const int64_t N = gy.size(0);
+  TORCH_CHECK(N > 0 && C > 0 && gy.size(1) % C == 0,
+              "row length must be C*HW");
+  const int64_t HW = gy.size(1) / C;
+  check_flat_bf16(gy, N, C, HW, "gy");
+  check_flat_bf16(y, N, C, HW, "y");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(gy.device());
+  Tensor gx = at::empty({N * HW, C}, gy.options());
+  Tensor partial = at::empty({bias_relu_flat_blocks(N), C},
+                             gy.options().dtype(at::kFloat));
+  Tensor grad_bias = at::empty({C}, gy.options().dtype(at::kFloat));
+  bias_relu_flat_bwd_launch(gy.data_ptr(), y.data_ptr(), gx.data_ptr(),
+                            partial.data_ptr<float>(),
+                            grad_bias.data_ptr<float>(), N, (int)C,
+                            (int)HW, current_stream());
+  return {gx, grad_bias};
+}
+
 Tensor tr16_probe(int64_t mode) {
   Tensor out = at::empty({64, 4}, at::TensorOptions()
                                       .dtype(at::kFloat)
@@ -522,4 +702,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fwd_bfrag_probe", &fwd_bfrag_probe);
   m.def("tr16_diag", &tr16_diag);
   m.def("conv1_fwd", &conv1_fwd);
+  m.def("conv1_fwd_relu", &conv1_fwd_relu);
+  m.def("conv1_wrw_masked", &conv1_wrw_masked);
+  m.def("bias_relu_", &bias_relu_);
+  m.def("bias_relu_bwd", &bias_relu_bwd);
+  m.def("bias_relu_flat", &bias_relu_flat);
+  m.def("bias_relu_flat_bwd", &bias_relu_flat_bwd);
 }

@@ -937,12 +937,20 @@ __device__ __forceinline__ int frag_slot(int lane) {
   return (lane >> 3) * 136 + (lane & 7) * 16;
 }
 
-__global__ __launch_bounds__(256)
-void conv1_wrw_v3_kernel(const __bf16* __restrict__ dy,
-                         const unsigned char* __restrict__ frames,
-                         float* __restrict__ out,
-                         float* __restrict__ b_out, int64_t K,
-                         int64_t k_per_wg, float scale) {
+// MASKED: the ReLU of the stem is fused into this kernel's dy load.
+// mask[k] holds the sign pattern of output row k (bit c set <=> the
+// activated output y[k][c] > 0, written by the fused forward); dy
+// elements whose bit is clear are zeroed before the fragment image is
+// written, so both the MFMA operand and the bias sum see
+// relu'(y) * dy and the 1 GB threshold_backward pass disappears.
+template <bool MASKED>
+__device__ __forceinline__
+void conv1_wrw_v3_body(const __bf16* __restrict__ dy,
+                       const unsigned int* __restrict__ mask,
+                       const unsigned char* __restrict__ frames,
+                       float* __restrict__ out,
+                       float* __restrict__ b_out, int64_t K,
+                       int64_t k_per_wg, float scale) {
   __shared__ __bf16 s_dy[2 * DY3_MT];
   __shared__ __bf16 s_x[16 * X3_NT];
 
@@ -990,7 +998,10 @@ void conv1_wrw_v3_kernel(const __bf16* __restrict__ dy,
       }
     }
   };
-  auto load_dy = [&](int64_t kc, bf16x4* ld) {
+  // the mask words ride along with the prefetched dy rows and are
+  // applied when the chunk is written to LDS, so the loads still
+  // complete under the previous chunk's MFMAs
+  auto load_dy = [&](int64_t kc, bf16x4* ld, unsigned int* mw) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       int64_t kk = kc + dy_kg * 8 + i;
@@ -1000,6 +1011,20 @@ void conv1_wrw_v3_kernel(const __bf16* __restrict__ dy,
 #pragma unroll
         for (int j = 0; j < 4; ++j) ld[i][j] = (__bf16)0.0f;
       }
+    }
+    if constexpr (MASKED) {
+      // the 8 rows of this lane start at a multiple of 8 (k_begin is a
+      // multiple of KC3) and K = batch*400 is one too, so the 8 words
+      // are 32 B aligned and all inside or all outside [0, k_end):
+      // two 16 B loads instead of eight 4 B ones
+      int64_t k0 = kc + dy_kg * 8;
+      uint4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
+      if (k0 < k_end) {
+        lo = *(const uint4*)(mask + k0);
+        hi = *(const uint4*)(mask + k0 + 4);
+      }
+      mw[0] = lo.x; mw[1] = lo.y; mw[2] = lo.z; mw[3] = lo.w;
+      mw[4] = hi.x; mw[5] = hi.y; mw[6] = hi.z; mw[7] = hi.w;
     }
   };
   auto store_x = [&](int ngc, int kg, const unsigned int* d) {
@@ -1019,9 +1044,10 @@ void conv1_wrw_v3_kernel(const __bf16* __restrict__ dy,
 
   unsigned int d1[8], d2[8];
   bf16x4 ldy[8];
+  unsigned int mw[8];
   load_x(k_begin, x_ngc, x_kg, d1);
   load_x(k_begin, x_ngc2, x_kg2, d2);
-  if (tid < 64) load_dy(k_begin, ldy);
+  if (tid < 64) load_dy(k_begin, ldy, mw);
 
   for (int64_t kc = k_begin; kc < k_end; kc += KC3) {
     // write the prefetched chunk into the fragment images
@@ -1033,7 +1059,13 @@ void conv1_wrw_v3_kernel(const __bf16* __restrict__ dy,
         int l = q * 16 + (m & 15);
         bf16x8 v;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = ldy[i][j];
+        for (int i = 0; i < 8; ++i) {
+          if constexpr (MASKED) {
+            v[i] = ((mw[i] >> m) & 1u) ? ldy[i][j] : (__bf16)0.0f;
+          } else {
+            v[i] = ldy[i][j];
+          }
+        }
         *(bf16x8*)(s_dy + (m >> 4) * DY3_MT + frag_slot(l)
                    + s * 8) = v;
       }
@@ -1047,7 +1079,7 @@ void conv1_wrw_v3_kernel(const __bf16* __restrict__ dy,
     if (kc + KC3 < k_end) {
       load_x(kc + KC3, x_ngc, x_kg, d1);
       load_x(kc + KC3, x_ngc2, x_kg2, d2);
-      if (tid < 64) load_dy(kc + KC3, ldy);
+      if (tid < 64) load_dy(kc + KC3, ldy, mw);
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -1082,6 +1114,27 @@ void conv1_wrw_v3_kernel(const __bf16* __restrict__ dy,
   }
 }
 
+__global__ __launch_bounds__(256)
+void conv1_wrw_v3_kernel(const __bf16* __restrict__ dy,
+                         const unsigned char* __restrict__ frames,
+                         float* __restrict__ out,
+                         float* __restrict__ b_out, int64_t K,
+                         int64_t k_per_wg, float scale) {
+  conv1_wrw_v3_body<false>(dy, nullptr, frames, out, b_out, K, k_per_wg,
+                           scale);
+}
+
+__global__ __launch_bounds__(256)
+void conv1_wrw_v3_masked_kernel(const __bf16* __restrict__ dy,
+                                const unsigned int* __restrict__ mask,
+                                const unsigned char* __restrict__ frames,
+                                float* __restrict__ out,
+                                float* __restrict__ b_out, int64_t K,
+                                int64_t k_per_wg, float scale) {
+  conv1_wrw_v3_body<true>(dy, mask, frames, out, b_out, K, k_per_wg,
+                          scale);
+}
+
 // fwd v3: 128 output rows per workgroup (16 MFMAs between barrier
 // pairs instead of 8) with register-prefetched frame loads — the PMC
 // run showed fwd 71% SQ_WAIT_ANY (waves parked on global latency in
@@ -1090,14 +1143,25 @@ void conv1_wrw_v3_kernel(const __bf16* __restrict__ dy,
 // ds_read_b128 shared across both m-tiles of the wave.
 // w image: addr(wn, l, pr) = wn*4624 + (l>>4)*1156 + (l&15)*72
 //          + pr*8   (4-elem pad per quarter, 8 per lane slot)
+//
+// RELU: the epilogue stores relu(bf16(acc + bias)) — the same bits as
+// relu applied to the plain kernel's output — and writes the sign
+// pattern of every output row as one 32-bit word (bit c set <=>
+// channel c > 0) for the masked weight-gradient kernel.
+// The stores stay sixteen 2-byte stores per lane: staging the tile
+// through s_x to leave as 16 B per lane was traced slower (1.49 vs
+// 1.39 ms at batch 40960, profiles/); it adds a barrier and an LDS
+// round trip, and the cause was not looked into further.
 #define FWD3_ROWS 128
 
-__global__ __launch_bounds__(256)
-void conv1_fwd_v3_kernel(const unsigned char* __restrict__ frames,
-                         const __bf16* __restrict__ weight,  // [256][32]
-                         const float* __restrict__ bias,
-                         __bf16* __restrict__ out, int64_t K,
-                         float scale) {
+template <bool RELU>
+__device__ __forceinline__
+void conv1_fwd_v3_body(const unsigned char* __restrict__ frames,
+                       const __bf16* __restrict__ weight,  // [256][32]
+                       const float* __restrict__ bias,
+                       __bf16* __restrict__ out,
+                       unsigned int* __restrict__ mask, int64_t K,
+                       float scale) {
   __shared__ __bf16 s_x[FWD3_ROWS * 32];
   __shared__ __bf16 s_w[2 * 4624];
 
@@ -1186,20 +1250,100 @@ void conv1_fwd_v3_kernel(const unsigned char* __restrict__ frames,
     __syncthreads();
   }
 
+  // epilogue (C/D map: col=lane&15, row=(lane>>4)*4+reg)
+  const int col0 = lane & 15;
+  const float bias0 = bias != nullptr ? bias[col0] : 0.0f;
+  const float bias1 = bias != nullptr ? bias[16 + col0] : 0.0f;
+  unsigned int row_mask = 0u;  // lanes 0..31: word of row wave*32+lane
 #pragma unroll
   for (int mt2 = 0; mt2 < 2; ++mt2) {
+    int row_base = wave * 32 + mt2 * 16 + (lane >> 4) * 4;
 #pragma unroll
-    for (int nt2 = 0; nt2 < 2; ++nt2) {
-      int col = nt2 * 16 + (lane & 15);
-      float b = bias != nullptr ? bias[col] : 0.0f;
-      int row_base = wave * 32 + mt2 * 16 + (lane >> 4) * 4;
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        int64_t kk = row0 + row_base + reg;
-        if (kk < K) {
-          out[kk * 32 + col] = (__bf16)(acc[mt2][nt2][reg] + b);
-        }
+    for (int reg = 0; reg < 4; ++reg) {
+      __bf16 v0 = (__bf16)(acc[mt2][0][reg] + bias0);
+      __bf16 v1 = (__bf16)(acc[mt2][1][reg] + bias1);
+      if constexpr (RELU) {
+        // !(v <= 0) keeps NaN, as ATen's relu does
+        bool p0 = !((float)v0 <= 0.0f);
+        bool p1 = !((float)v1 <= 0.0f);
+        // ballot bit l = lane l = (row group l>>4, column l&15): the
+        // 16-bit field q of the two ballots is the word of row
+        // mt2*16 + q*4 + reg; lane l < 32 keeps the word of row l
+        unsigned long long m0 = __ballot(p0);
+        unsigned long long m1 = __ballot(p1);
+        int q = (lane >> 2) & 3;
+        unsigned int w =
+            (unsigned int)((m0 >> (q * 16)) & 0xFFFFull)
+            | ((unsigned int)((m1 >> (q * 16)) & 0xFFFFull) << 16);
+        if ((lane >> 4) == mt2 && (lane & 3) == reg) row_mask = w;
+        v0 = p0 ? v0 : (__bf16)0.0f;
+        v1 = p1 ? v1 : (__bf16)0.0f;
+      }
+      int64_t kk = row0 + row_base + reg;
+      if (kk < K) {
+        out[kk * 32 + col0] = v0;
+        out[kk * 32 + 16 + col0] = v1;
       }
     }
   }
+  if constexpr (RELU) {
+    int64_t kk = row0 + wave * 32 + lane;
+    if (lane < 32 && kk < K) mask[kk] = row_mask;
+  }
+}
+
+__global__ __launch_bounds__(256)
+void conv1_fwd_v3_kernel(const unsigned char* __restrict__ frames,
+                         const __bf16* __restrict__ weight,
+                         const float* __restrict__ bias,
+                         __bf16* __restrict__ out, int64_t K,
+                         float scale) {
+  conv1_fwd_v3_body<false>(frames, weight, bias, out, nullptr, K, scale);
+}
+
+__global__ __launch_bounds__(256)
+void conv1_fwd_v3_relu_kernel(const unsigned char* __restrict__ frames,
+                              const __bf16* __restrict__ weight,
+                              const float* __restrict__ bias,
+                              __bf16* __restrict__ out,
+                              unsigned int* __restrict__ mask, int64_t K,
+                              float scale) {
+  conv1_fwd_v3_body<true>(frames, weight, bias, out, mask, K, scale);
+}
+
+// fused-activation entry points (v3 kernels only)
+void conv1_fwd_relu_launch(const unsigned char* frames, const void* weight,
+                           const float* bias, void* out,
+                           unsigned int* mask, int64_t K, float scale,
+                           hipStream_t stream) {
+  int64_t grid = (K + FWD3_ROWS - 1) / FWD3_ROWS;
+  hipLaunchKernelGGL(conv1_fwd_v3_relu_kernel, dim3((unsigned)grid),
+                     dim3(256), 0, stream, frames, (const __bf16*)weight,
+                     bias, (__bf16*)out, mask, K, scale);
+  HIP_CHECK(hipGetLastError());
+}
+
+void conv1_wrw_masked_launch(const void* dy, const unsigned int* mask,
+                             const unsigned char* frames, float* scratch,
+                             float* grad_w, float* grad_b, int64_t K,
+                             float scale, hipStream_t stream) {
+  HIP_CHECK(hipMemsetAsync(scratch, 0,
+                           CONV1_COUT * CONV1_N * sizeof(float), stream));
+  HIP_CHECK(hipMemsetAsync(grad_b, 0, CONV1_COUT * sizeof(float),
+                           stream));
+  int64_t target_wg = 2048;
+  if (const char* e = getenv("MACHIN_CONV1_WG")) target_wg = atol(e);
+  if (target_wg < 1) target_wg = 1;
+  int64_t k_per_wg = (K + target_wg - 1) / target_wg;
+  k_per_wg = ((k_per_wg + KC3 - 1) / KC3) * KC3;
+  if (k_per_wg < KC3) k_per_wg = KC3;
+  int grid = (int)((K + k_per_wg - 1) / k_per_wg);
+  hipLaunchKernelGGL(conv1_wrw_v3_masked_kernel, dim3(grid), dim3(256), 0,
+                     stream, (const __bf16*)dy, mask, frames, scratch,
+                     grad_b, K, k_per_wg, scale);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(conv1_wrw_reorder_kernel,
+                     dim3((CONV1_COUT * CONV1_N + 255) / 256), dim3(256),
+                     0, stream, scratch, grad_w);
+  HIP_CHECK(hipGetLastError());
 }

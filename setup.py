@@ -29,6 +29,7 @@ SOURCES = [
     "elementwise.hip",
     "framestack.hip",
     "conv1_wrw.hip",
+    "bias_act.hip",
 ]
 
 
