@@ -86,7 +86,38 @@ class RAINBOW(DQNPer):
     # ------------------------------------------------------------------
     def store_episode(self, episode: List[Union[Transition, Dict]]):
         """Fold the next ``reward_future_steps`` rewards into each
-        transition before storing (n-step returns)."""
+        transition before storing (n-step returns).
+
+        A replay buffer that folds n-step returns itself when sampling
+        (``replay_buffer.n_step > 1``, see
+        :class:`..buffers.frame_stack_buffer.DeviceFrameStackBuffer`)
+        gets the raw 1-step episode instead; its ``n_step`` and
+        ``discount`` must equal this algorithm's
+        ``reward_future_steps`` and ``discount``. Sampled rows are then
+        what the host fold stores, and ``update`` bootstraps every
+        sample with ``discount ** reward_future_steps`` on both paths,
+        windows cut short by the episode's end included; the buffer
+        also returns the per-sample step count ``m`` as the custom
+        attribute ``n_step`` for users who want ``discount ** m``.
+        """
+        buffer_n = getattr(self.replay_buffer, "n_step", 1)
+        if buffer_n > 1:
+            buffer_discount = self.replay_buffer.discount
+            if buffer_n != self.reward_future_steps \
+                    or abs(buffer_discount - self.discount) >= 1e-12:
+                raise ValueError(
+                    f"Replay buffer folds n-step returns with n_step="
+                    f"{buffer_n}, discount={buffer_discount}, but the "
+                    f"algorithm has reward_future_steps="
+                    f"{self.reward_future_steps}, discount="
+                    f"{self.discount}."
+                )
+            self.replay_buffer.store_episode(
+                episode,
+                required_attrs=("state", "action", "next_state", "reward",
+                                "terminal"),
+            )
+            return
         episode = [
             Transition(**tr) if isinstance(tr, dict) else tr for tr in episode
         ]

@@ -20,6 +20,12 @@ Layout:
   written at slot ``s`` has base ``s + t``; its state is planes
   ``base .. base+k-1`` and its next_state planes ``base+1 .. base+k``.
 
+With ``n_step > 1`` the transition ring also holds the number of
+transitions left in the episode, and sampling uses
+:func:`machin_amd.ops.framestack_gather_nstep`, which folds RAINBOW's
+n-step reward / terminal / ``next_state = state_{t+m}`` from the raw
+1-step rows in the same kernel (see the class docstring).
+
 Eviction is by overwritten planes. All bookkeeping is host integers
 (absolute plane / transition counters and a deque of ``(first base,
 count)`` per episode), so neither storing nor sampling waits for the
@@ -66,6 +72,26 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
     transitions whose base lies in that range (windows look forward and
     never leave their own episode's slots), oldest first, so live
     transitions stay a contiguous range of the transition ring.
+
+    ``n_step > 1`` (at most 16) turns on n-step sampling for RAINBOW:
+    episodes are still stored RAW, one step per transition, plus one
+    int64 column with the number of transitions left in the episode,
+    and :func:`machin_amd.ops.framestack_gather_nstep` folds the
+    n-step return when sampling. A sampled transition ``t`` with
+    ``m = min(n_step, L - t)`` comes back with ``reward = sum_{j<m}
+    discount^j r_{t+j}`` (cut at a terminal), ``terminal = max_{j<m}
+    terminal_{t+j}``, ``next_state = state_{t+m}`` and the custom
+    attribute ``n_step = m`` (``[B, 1]`` int64, under ``"*"``) — the
+    rows RAINBOW's host fold would have stored. ``reward`` and
+    ``terminal`` must be scalar float32 columns.
+
+    Eviction, priorities and ``size()`` are the same for every
+    ``n_step``: a window only looks FORWARD, at the ``m + k`` planes
+    from its base on (inside the episode's ``L + k`` slots, since
+    ``t + m <= L``) and at the next ``m - 1`` transitions of its own
+    episode. Planes and transitions are both overwritten oldest first,
+    so everything a live transition's window needs was written after
+    its base plane and outlives it.
     """
 
     def __init__(
@@ -77,15 +103,22 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
         frame_layout: str = "nchw",
         prioritized: bool = False,
         validate: bool = True,
+        n_step: int = 1,
+        discount: float = 0.99,
         **per_kwargs,
     ):
         super().__init__(buffer_size, device, prioritized, **per_kwargs)
         self.frame_stack = int(frame_stack)
         if not 1 <= self.frame_stack <= 8:
             raise ValueError("frame_stack must be in [1, 8].")
-        if self.buffer_size < self.frame_stack + 1:
+        self.n_step = int(n_step)
+        if not 1 <= self.n_step <= 16:
+            raise ValueError("n_step must be in [1, 16].")
+        self.discount = float(discount)
+        if self.buffer_size < self.frame_stack + self.n_step:
             raise ValueError(
-                "buffer_size (frames) must be at least frame_stack + 1."
+                "buffer_size (frames) must be at least frame_stack + "
+                "n_step."
             )
         if frame_layout not in ("nchw", "nhwc"):
             raise ValueError("frame_layout must be 'nchw' or 'nhwc'.")
@@ -132,7 +165,8 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
             self._tree = DeviceSumTree(self._t_capacity, dev)
             self._max_priority = t.ones((), device=dev)
         self._attr_order = sorted(
-            {k.split("/", 1)[0] for k in spec if k != "_base"}
+            {k.split("/", 1)[0] for k in spec
+             if k not in ("_base", "_left")}
             | {"state", "next_state"}
         )
 
@@ -191,6 +225,16 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
             F, T = self.buffer_size, self._t_capacity
             first = self._plane_count
             cols["_base"] = t.arange(first, first + L, dtype=t.int64) % F
+            if self.n_step > 1:
+                for name in ("reward", "terminal"):
+                    v = cols.get(name)
+                    if v is None or v.dim() != 1 or v.dtype != t.float32:
+                        raise ValueError(
+                            f"n_step > 1 needs {name!r} as a scalar "
+                            f"float32 column."
+                        )
+                # transitions that follow in the episode
+                cols["_left"] = t.arange(L - 1, -1, -1, dtype=t.int64)
             self._ensure_rings(cols, tuple(frames.shape[1:]))
             # refuse before any bookkeeping changes
             if frames.shape[1:] != self._planes.shape[1:]:
@@ -301,11 +345,29 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
                 )
             else:
                 pos = self._uniform_live(batch_size)
-            cols = self._inner.gather(pos)
-            state, next_state = ops.framestack_gather(
-                self._planes, cols.pop("_base"), self.frame_stack,
-                channels_last=self.frame_layout == "nhwc",
-            )
+            if self.n_step > 1:
+                # the kernel indexes these four ring columns itself
+                data = self._inner.data
+                fused = ("_base", "_left", "reward", "terminal")
+                cols = {
+                    k: buf.index_select(0, pos)
+                    for k, buf in data.items() if k not in fused
+                }
+                (
+                    state, next_state, cols["reward"], cols["terminal"],
+                    steps,
+                ) = ops.framestack_gather_nstep(
+                    self._planes, *(data[k] for k in fused), pos,
+                    self.frame_stack, self.n_step, self.discount,
+                    channels_last=self.frame_layout == "nhwc",
+                )
+                cols["n_step"] = steps.view(-1, 1)
+            else:
+                cols = self._inner.gather(pos)
+                state, next_state = ops.framestack_gather(
+                    self._planes, cols.pop("_base"), self.frame_stack,
+                    channels_last=self.frame_layout == "nhwc",
+                )
             cols[self._state_col] = state
             cols[self._next_col] = next_state
             attrs = sample_attrs or (self._attr_order + ["*"])

@@ -587,10 +587,126 @@ def framestack_gather(
     return _framestack_gather_torch(planes, base, k, bool(channels_last))
 
 
+def _framestack_gather_nstep_torch(
+    planes: t.Tensor, base: t.Tensor, left: t.Tensor, reward: t.Tensor,
+    terminal: t.Tensor, pos: t.Tensor, k: int, n: int, gamma: float,
+    channels_last: bool,
+):
+    """Torch composition of :func:`framestack_gather_nstep` (the CPU
+    path and the reference the kernel is tested and timed against)."""
+    P, T = planes.shape[0], base.shape[0]
+    dev = pos.device
+    # python-style % is non-negative
+    p = pos.long() % T
+    s = base.index_select(0, p) % P
+    m = left.index_select(0, p).clamp(0, n - 1) + 1
+    fmt = t.channels_last if channels_last else t.contiguous_format
+    ar_k = t.arange(k, device=dev).view(1, -1)
+
+    def stack(first):
+        idx = (first.view(-1, 1) + ar_k) % P
+        return planes.index_select(0, idx.view(-1)).view(
+            -1, k, *planes.shape[1:]
+        ).contiguous(memory_format=fmt)
+
+    ar_n = t.arange(n, device=dev).view(1, -1)
+    q = ((p.view(-1, 1) + ar_n) % T).view(-1)
+    r = reward.index_select(0, q).view(-1, n)
+    d = terminal.index_select(0, q).view(-1, n)
+    inside = ar_n < m.view(-1, 1)
+    # fp32, in the kernel's order: acc += disc * r; disc *= gamma * (1 - d)
+    acc = t.zeros_like(r[:, 0])
+    disc = t.ones_like(acc)
+    zero = t.zeros_like(acc)
+    for j in range(n):
+        acc = acc + t.where(inside[:, j], disc * r[:, j], zero)
+        disc = disc * (gamma * (1.0 - d[:, j]))
+    terminal_n = t.where(
+        inside, d, t.full_like(d, float("-inf"))
+    ).amax(dim=1)
+    return stack(s), stack(s + m), acc, terminal_n, m
+
+
+def framestack_gather_nstep(
+    planes: t.Tensor, base: t.Tensor, left: t.Tensor, reward: t.Tensor,
+    terminal: t.Tensor, pos: t.Tensor, k: int, n: int, gamma: float,
+    channels_last: bool = False,
+):
+    """:func:`framestack_gather` with n-step returns computed when
+    sampling, from raw 1-step episodes: returns ``(state, next_state,
+    reward_n, terminal_n, steps)``.
+
+    ``planes`` is the u8 frame ring ``[P, H, W]``; ``base`` (int64),
+    ``left`` (int64), ``reward`` (f32) and ``terminal`` (f32) are the
+    WHOLE transition-ring columns ``[T]``, with ``left[p]`` the number
+    of transitions that follow ``p`` inside its episode; ``pos`` int64
+    ``[B]`` holds the sampled transition-ring positions. Limits:
+    ``1 <= k <= 8``, ``1 <= n <= 16``, ``P >= k + n``, ``T >= 1``.
+
+    For sample ``b`` (every modulo non-negative, so no value of
+    ``pos``, ``base`` or ``left`` addresses outside either ring)::
+
+        p = pos[b] mod T;  s = base[p] mod P
+        m = clamp(left[p], 0, n-1) + 1;  q_j = (p + j) mod T
+        reward_n[b]   = sum_{j<m} gamma^j reward[q_j]
+                                  prod_{i<j} (1 - terminal[q_i])   (fp32)
+        terminal_n[b] = max_{j<m} terminal[q_j]
+        steps[b]      = m                                          (int64)
+        state[b, j]      = planes[(s + j) mod P]        j < k
+        next_state[b, j] = planes[(s + m + j) mod P]    j < k
+
+    ``reward_n`` is the definition of :func:`nstep_returns`; ``m`` does
+    not stop early at a terminal (a terminal inside the window only
+    sets ``terminal_n``), which is what RAINBOW's host fold stores.
+    The stacks are u8 ``[B, k, H, W]``, contiguous or
+    ``channels_last``, as in :func:`framestack_gather`; with ``n == 1``
+    they are the stacks of ``framestack_gather(planes, base[pos], k)``
+    and ``reward_n`` / ``terminal_n`` the stored values.
+
+    On ROCm the whole op is one gfx950 kernel launch
+    (machin_amd/ops/hip/framestack.hip); the CPU fallback is the same
+    semantics as a torch composition.
+    """
+    k, n = int(k), int(n)
+    if planes.is_cuda:
+        ext = _require_ext()
+        return tuple(ext.framestack_gather_nstep(
+            planes, base, left, reward, terminal, pos, k, n, float(gamma),
+            bool(channels_last),
+        ))
+    if planes.dim() != 3 or planes.dtype != t.uint8:
+        raise ValueError("planes must be a uint8 [P, H, W] ring")
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in [1, 8]")
+    if not 1 <= n <= 16:
+        raise ValueError("n must be in [1, 16]")
+    if planes.shape[0] < k + n:
+        raise ValueError("ring needs at least k+n planes")
+    for name, col, dtype in (
+        ("base", base, t.int64), ("left", left, t.int64),
+        ("reward", reward, t.float32), ("terminal", terminal, t.float32),
+        ("pos", pos, t.int64),
+    ):
+        if col.dim() != 1 or col.dtype != dtype:
+            raise ValueError(f"{name} must be a 1-D {dtype} tensor")
+    T = base.shape[0]
+    if T < 1 or not left.shape[0] == reward.shape[0] == \
+            terminal.shape[0] == T:
+        raise ValueError(
+            "base, left, reward and terminal must be non-empty columns "
+            "of the same length"
+        )
+    return _framestack_gather_nstep_torch(
+        planes, base, left, reward, terminal, pos, k, n, float(gamma),
+        bool(channels_last),
+    )
+
+
 __all__ = [
     "available",
     "dequant_u8",
     "framestack_gather",
+    "framestack_gather_nstep",
     "polyak_update_",
     "discounted_returns",
     "gae",

@@ -53,6 +53,11 @@ void u8_to_bf16_scale_launch(const unsigned char*, void*, int64_t, float,
 void framestack_gather_launch(const unsigned char*, const int64_t*,
                               unsigned char*, unsigned char*, int64_t,
                               int64_t, int64_t, int, bool, hipStream_t);
+void framestack_gather_nstep_launch(
+    const unsigned char*, const int64_t*, const int64_t*, const float*,
+    const float*, const int64_t*, unsigned char*, unsigned char*, float*,
+    float*, int64_t*, int64_t, int64_t, int64_t, int64_t, int, int, float,
+    bool, hipStream_t);
 void pg_head_fwd_launch(const void*, const int64_t*, float*, float*,
                         int64_t, int, hipStream_t);
 void pg_head_bwd_launch(const void*, const int64_t*, const float*,
@@ -414,6 +419,64 @@ std::vector<Tensor> framestack_gather(Tensor planes, Tensor base, int64_t k,
   return {state, next};
 }
 
+// n-step variant: the kernel indexes the whole transition-ring columns
+// base/left/reward/terminal [T] with the sampled positions pos [B] and
+// returns (state, next_state, reward_n, terminal_n, steps); semantics
+// in framestack.hip. All indices are reduced or clamped in the kernel.
+std::vector<Tensor> framestack_gather_nstep(Tensor planes, Tensor base,
+                                            Tensor left, Tensor reward,
+                                            Tensor terminal, Tensor pos,
+                                            int64_t k, int64_t n,
+                                            double gamma,
+                                            bool channels_last) {
+  TORCH_CHECK(planes.is_cuda() && planes.scalar_type() == at::kByte &&
+                  planes.is_contiguous(),
+              "planes must be contiguous uint8 CUDA");
+  TORCH_CHECK(planes.dim() == 3, "planes must be [P, H, W]");
+  TORCH_CHECK(k >= 1 && k <= 8, "k must be in [1, 8]");
+  TORCH_CHECK(n >= 1 && n <= 16, "n must be in [1, 16]");
+  const int64_t P = planes.size(0), H = planes.size(1), W = planes.size(2);
+  TORCH_CHECK(P >= k + n, "ring needs at least k+n planes");
+  TORCH_CHECK(H * W > 0, "planes must not be empty");
+  const int64_t T = base.numel();
+  TORCH_CHECK(T >= 1, "transition ring needs at least one row");
+  for (const Tensor* c : {&base, &left, &pos}) {
+    TORCH_CHECK(c->is_cuda() && c->scalar_type() == at::kLong &&
+                    c->is_contiguous() && c->dim() == 1,
+                "base, left and pos must be contiguous 1-D int64 CUDA");
+  }
+  for (const Tensor* c : {&reward, &terminal}) {
+    TORCH_CHECK(c->is_cuda() && c->scalar_type() == at::kFloat &&
+                    c->is_contiguous() && c->dim() == 1,
+                "reward and terminal must be contiguous 1-D float32 CUDA");
+  }
+  for (const Tensor* c : {&base, &left, &reward, &terminal, &pos}) {
+    TORCH_CHECK(c->device() == planes.device(),
+                "all tensors must be on the same device");
+  }
+  TORCH_CHECK(left.numel() == T && reward.numel() == T &&
+                  terminal.numel() == T,
+              "base, left, reward and terminal must have the same length");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(planes.device());
+  const int64_t B = pos.numel();
+  const auto fmt = channels_last ? at::MemoryFormat::ChannelsLast
+                                 : at::MemoryFormat::Contiguous;
+  Tensor state = at::empty({B, k, H, W}, planes.options(), fmt);
+  Tensor next = at::empty({B, k, H, W}, planes.options(), fmt);
+  Tensor reward_n = at::empty({B}, reward.options());
+  Tensor terminal_n = at::empty({B}, reward.options());
+  Tensor steps = at::empty({B}, pos.options());
+  framestack_gather_nstep_launch(
+      planes.data_ptr<unsigned char>(), base.data_ptr<int64_t>(),
+      left.data_ptr<int64_t>(), reward.data_ptr<float>(),
+      terminal.data_ptr<float>(), pos.data_ptr<int64_t>(),
+      state.data_ptr<unsigned char>(), next.data_ptr<unsigned char>(),
+      reward_n.data_ptr<float>(), terminal_n.data_ptr<float>(),
+      steps.data_ptr<int64_t>(), B, P, T, H * W, (int)k, (int)n,
+      (float)gamma, channels_last, current_stream());
+  return {state, next, reward_n, terminal_n, steps};
+}
+
 std::vector<Tensor> conv1_wrw(Tensor dy, Tensor frames, double scale) {
   // dy: [K, 32] bf16 (NHWC-flattened conv output grad);
   // frames: [B, 84, 84, 4] u8. Returns [32, 4, 8, 8] fp32 grad.
@@ -694,6 +757,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ou_update_", &ou_update_);
   m.def("u8_to_bf16_scale", &u8_to_bf16_scale);
   m.def("framestack_gather", &framestack_gather);
+  m.def("framestack_gather_nstep", &framestack_gather_nstep);
   m.def("pg_head_fwd", &pg_head_fwd);
   m.def("pg_head_bwd", &pg_head_bwd);
   m.def("conv1_wrw", &conv1_wrw);

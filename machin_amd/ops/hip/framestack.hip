@@ -20,6 +20,9 @@
 // No LDS, no atomics. `base` is reduced into [0, P) in the kernel
 // (non-negative modulo), so no int64 value can address outside the
 // ring and the host never has to look at the values.
+//
+// The second half of the file is the n-step variant of the same
+// gather (framestack_gather_nstep_launch).
 #include "common.h"
 
 typedef unsigned char u8;
@@ -198,4 +201,198 @@ void framestack_gather_launch(const unsigned char* planes,
   hipLaunchKernelGGL(framestack_scalar_kernel,
                      dim3(ma_grid(B * HW, block)), dim3(block), 0, stream,
                      planes, base, state, next, B, P, HW, k, nhwc);
+}
+
+// =====================================================================
+// n-step gather: n-step returns computed WHEN SAMPLING, from raw
+// 1-step episodes. The kernel gets the whole transition-ring columns
+// base/left/reward/terminal [T] and the sampled ring positions pos [B]
+// and indexes the columns itself. For sample b:
+//   p = pos[b] mod T,  s = base[p] mod P,
+//   m = clamp(left[p], 0, n-1) + 1        (transitions in the window)
+//   state[b, j]      = planes[(s + j) mod P]
+//   next_state[b, j] = planes[(s + m + j) mod P]          j < k
+//   reward_n[b]   = sum_{j<m} gamma^j reward[q_j] prod_{i<j} (1 - terminal[q_i])
+//   terminal_n[b] = max_{j<m} terminal[q_j],   q_j = (p + j) mod T
+//   steps[b]      = m
+// Every index is reduced or clamped in the kernel, so no value of pos,
+// base or left can address outside either ring (P >= k + n is checked
+// by the binding: s + m + j < 2P for fs_slot).
+//
+// Same work decomposition as above (one item = 16 pixels, or one
+// pixel, of one sample); every item reads base[p] and left[p] (two
+// cached 8-byte loads), and the item that owns chunk 0 of a sample
+// also walks its <= n reward/terminal entries and writes the three
+// per-sample scalars. One launch, no LDS, no atomics.
+// =====================================================================
+struct fs_nstep_args {
+  const int64_t* __restrict__ base;     // [T]
+  const int64_t* __restrict__ left;     // [T]
+  const float* __restrict__ reward;     // [T]
+  const float* __restrict__ terminal;   // [T]
+  const int64_t* __restrict__ pos;      // [B]
+  float* __restrict__ reward_n;         // [B]
+  float* __restrict__ terminal_n;       // [B]
+  int64_t* __restrict__ steps;          // [B]
+  int64_t B, P, T;
+  int n;
+  float gamma;
+};
+
+// p, s and m of sample b
+__device__ __forceinline__ void fs_nstep_window(const fs_nstep_args& a,
+                                                int64_t b, int64_t& p,
+                                                int64_t& s, int& m) {
+  p = a.pos[b] % a.T;
+  if (p < 0) p += a.T;
+  s = fs_base(a.base, p, a.P);
+  int64_t l = a.left[p];
+  l = l < 0 ? 0 : (l > a.n - 1 ? a.n - 1 : l);
+  m = (int)l + 1;
+}
+
+// the three per-sample scalars (called by one item per sample)
+__device__ __forceinline__ void fs_nstep_scalars(const fs_nstep_args& a,
+                                                 int64_t b, int64_t p,
+                                                 int m) {
+  float acc = 0.0f, disc = 1.0f, tmax = 0.0f;
+  int64_t q = p;
+  for (int j = 0; j < m; ++j) {
+    const float r = a.reward[q], d = a.terminal[q];
+    acc += disc * r;
+    tmax = j == 0 ? d : fmaxf(tmax, d);
+    disc *= a.gamma * (1.0f - d);
+    if (++q == a.T) q = 0;
+  }
+  a.reward_n[b] = acc;
+  a.terminal_n[b] = tmax;
+  a.steps[b] = m;
+}
+
+// Vector paths: 2k dwordx4 loads per item, k for each stack. When
+// m < k the stacks share k - m planes; the second load of a shared
+// chunk comes from the same lane and is served by the cache, so HBM
+// traffic is k + min(m, k) plane reads. Keeping the shared chunks in
+// registers instead (k + m loads, one compile-time case per m < k)
+// was measured and is not faster: docs/PERFORMANCE.md.
+template <int K>
+__global__ void framestack_nstep_nchw_vec_kernel(
+    const uint4* __restrict__ planes, uint4* __restrict__ state,
+    uint4* __restrict__ next, fs_nstep_args a, int64_t C) {
+  const int64_t total = a.B * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / C, c = i - b * C;
+    int64_t p, s;
+    int m;
+    fs_nstep_window(a, b, p, s, m);
+    uint4 v[K], w[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      v[j] = planes[fs_slot(s, j, a.P) * C + c];
+      w[j] = planes[fs_slot(s, m + j, a.P) * C + c];
+    }
+    const int64_t o = b * K * C + c;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      state[o + j * C] = v[j];
+      next[o + j * C] = w[j];
+    }
+    if (c == 0) fs_nstep_scalars(a, b, p, m);
+  }
+}
+
+// NHWC k == 4 vector path
+__global__ void framestack_nstep_nhwc4_vec_kernel(
+    const uint4* __restrict__ planes, uint4* __restrict__ state,
+    uint4* __restrict__ next, fs_nstep_args a, int64_t C) {
+  const int64_t total = a.B * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / C, c = i - b * C;
+    int64_t p, s;
+    int m;
+    fs_nstep_window(a, b, p, s, m);
+    uint4 v[4], w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = planes[fs_slot(s, j, a.P) * C + c];
+      w[j] = planes[fs_slot(s, m + j, a.P) * C + c];
+    }
+    fs_store_nhwc4(state + 4 * i, v[0], v[1], v[2], v[3]);
+    fs_store_nhwc4(next + 4 * i, w[0], w[1], w[2], w[3]);
+    if (c == 0) fs_nstep_scalars(a, b, p, m);
+  }
+}
+
+// scalar path: one work item = one pixel of one sample
+__global__ void framestack_nstep_scalar_kernel(
+    const u8* __restrict__ planes, u8* __restrict__ state,
+    u8* __restrict__ next, fs_nstep_args a, int64_t HW, int k, bool nhwc) {
+  const int64_t total = a.B * HW;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / HW, px = i - b * HW;
+    int64_t p, s;
+    int m;
+    fs_nstep_window(a, b, p, s, m);
+    const int64_t o = nhwc ? i * k : b * k * HW + px;
+    const int64_t step = nhwc ? 1 : HW;
+    for (int j = 0; j < k; ++j) {
+      state[o + j * step] = planes[fs_slot(s, j, a.P) * HW + px];
+      next[o + j * step] = planes[fs_slot(s, m + j, a.P) * HW + px];
+    }
+    if (px == 0) fs_nstep_scalars(a, b, p, m);
+  }
+}
+
+template <int K>
+static void fs_launch_nstep_nchw_vec(const u8* planes, u8* state, u8* next,
+                                     const fs_nstep_args& a, int64_t C,
+                                     hipStream_t stream) {
+  const int block = 256;
+  hipLaunchKernelGGL(framestack_nstep_nchw_vec_kernel<K>,
+                     dim3(ma_grid(a.B * C, block)), dim3(block), 0, stream,
+                     (const uint4*)planes, (uint4*)state, (uint4*)next, a,
+                     C);
+}
+
+void framestack_gather_nstep_launch(
+    const unsigned char* planes, const int64_t* base, const int64_t* left,
+    const float* reward, const float* terminal, const int64_t* pos,
+    unsigned char* state, unsigned char* next, float* reward_n,
+    float* terminal_n, int64_t* steps, int64_t B, int64_t P, int64_t T,
+    int64_t HW, int k, int n, float gamma, bool nhwc, hipStream_t stream) {
+  if (B == 0) return;
+  const fs_nstep_args a = {base,     left,       reward, terminal, pos,
+                           reward_n, terminal_n, steps,  B,        P,
+                           T,        n,          gamma};
+  const int block = 256;
+  const bool aligned =
+      (((uintptr_t)planes | (uintptr_t)state | (uintptr_t)next) & 15) == 0;
+  const bool vec = (HW % 16 == 0) && aligned;
+  const int64_t C = HW / 16;
+  if (vec && !nhwc) {
+    switch (k) {
+      case 1: fs_launch_nstep_nchw_vec<1>(planes, state, next, a, C, stream); return;
+      case 2: fs_launch_nstep_nchw_vec<2>(planes, state, next, a, C, stream); return;
+      case 3: fs_launch_nstep_nchw_vec<3>(planes, state, next, a, C, stream); return;
+      case 4: fs_launch_nstep_nchw_vec<4>(planes, state, next, a, C, stream); return;
+      case 5: fs_launch_nstep_nchw_vec<5>(planes, state, next, a, C, stream); return;
+      case 6: fs_launch_nstep_nchw_vec<6>(planes, state, next, a, C, stream); return;
+      case 7: fs_launch_nstep_nchw_vec<7>(planes, state, next, a, C, stream); return;
+      case 8: fs_launch_nstep_nchw_vec<8>(planes, state, next, a, C, stream); return;
+      default: break;
+    }
+  }
+  if (vec && nhwc && k == 4) {
+    hipLaunchKernelGGL(framestack_nstep_nhwc4_vec_kernel,
+                       dim3(ma_grid(B * C, block)), dim3(block), 0, stream,
+                       (const uint4*)planes, (uint4*)state, (uint4*)next, a,
+                       C);
+    return;
+  }
+  hipLaunchKernelGGL(framestack_nstep_scalar_kernel,
+                     dim3(ma_grid(B * HW, block)), dim3(block), 0, stream,
+                     planes, state, next, a, HW, k, nhwc);
 }

@@ -1,6 +1,6 @@
 """Time the frame-stack gather of the frame-deduplicated replay.
 
-    python tools/bench_framestack.py [--out table.md]
+    python tools/bench_framestack.py [--out table.md] [--n-step N]
 
 For 84x84 frames, k=4 and B in {32, 512, 4096}, in both output
 layouts, three ways of producing one sampled (state, next_state)
@@ -21,6 +21,20 @@ each is warmed up and timed with device events over ``--iters`` calls,
 median round is reported with the min-max spread. Indices are fresh
 random draws per call from a ring larger than the 256 MiB Infinity
 Cache, as in a real replay. Needs a GPU; there is no CPU mode.
+
+With ``--n-step N`` (N > 1) the table is about
+``ops.framestack_gather_nstep`` instead, same shapes and method, on a
+transition ring of ``--frames`` rows cut into episodes of 1000 steps
+(so nearly every window has m = N):
+
+* nstep kernel — ``ops.framestack_gather_nstep`` (one gfx950 kernel);
+* nstep torch  — the same result as a torch composition over the same
+                 rings (``ops._framestack_gather_nstep_torch``);
+* 1-step kernel — ``ops.framestack_gather`` on the same draws (the
+                 base column is the identity, so ``base[pos]`` is
+                 ``pos``), timed in the same rounds: the n-step
+                 kernel's ratio to it is printed next to the ratio of
+                 the plane bytes the two must move.
 """
 import argparse
 import json
@@ -59,6 +73,91 @@ def time_ms(fn, draws, iters):
     return start.elapsed_time(stop) / iters
 
 
+def nstep_table(args, dev):
+    """Rows for ops.framestack_gather_nstep (see the module docstring)."""
+    n, gamma, L = args.n_step, 0.99, 1000
+    P = T = args.frames
+    ring = t.randint(0, 256, (P, H, W), dtype=t.uint8, device=dev)
+    base = t.arange(T, device=dev)
+    left = (L - 1) - t.arange(T, device=dev) % L
+    reward = t.randn(T, device=dev)
+    terminal = (left == 0).float()
+    m = min(n, K)
+    # plane bytes: k + min(m, k) reads and 2k writes, against k+1 and 2k
+    nstep_planes, one_planes = 3 * K + m, 3 * K + 1
+
+    rows = []
+    for nhwc in (False, True):
+        def nstep_kernel(pos):
+            return ops.framestack_gather_nstep(
+                ring, base, left, reward, terminal, pos, K, n, gamma, nhwc)
+
+        def nstep_torch(pos):
+            return ops._framestack_gather_nstep_torch(
+                ring, base, left, reward, terminal, pos, K, n, gamma, nhwc)
+
+        def one_step_kernel(pos):
+            # base is the identity here, so base[pos] == pos
+            return ops.framestack_gather(ring, pos, K, nhwc)
+
+        variants = [("nstep", nstep_kernel), ("torch", nstep_torch),
+                    ("onestep", one_step_kernel)]
+        for B in (32, 512, 4096):
+            draws = [t.randint(0, T, (B,), device=dev) for _ in range(16)]
+            want, got = nstep_kernel(draws[0]), nstep_torch(draws[0])
+            for i in (0, 1, 3, 4):
+                assert t.equal(got[i], want[i])
+                assert got[i].stride() == want[i].stride()
+            assert t.allclose(got[2], want[2], rtol=1e-5, atol=1e-6)
+            for _, fn in variants:
+                time_ms(fn, draws, 20)  # warm-up
+            samples = {name: [] for name, _ in variants}
+            for _ in range(args.rounds):
+                for name, fn in variants:
+                    samples[name].append(time_ms(fn, draws, args.iters))
+            row = {"layout": "nhwc" if nhwc else "nchw", "B": B, "n": n}
+            for name, vals in samples.items():
+                row[name + "_ms"] = statistics.median(vals)
+                row[name + "_min_ms"] = min(vals)
+                row[name + "_max_ms"] = max(vals)
+            row["nstep_GBps"] = (
+                B * nstep_planes * H * W / (row["nstep_ms"] * 1e-3) / 1e9
+            )
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+
+    lines = [
+        f"| layout | B | n-step kernel ms (min-max), n={n} | "
+        "torch, same rings ms | 1-step kernel ms (min-max) | "
+        "n-step kernel GB/s | torch / n-step kernel | "
+        f"n-step / 1-step kernel (bytes: {nstep_planes}/{one_planes} = "
+        f"{nstep_planes / one_planes:.3f}) |",
+        "|---|---|---|---|---|---|---|---|",
+    ]
+    for r in rows:
+        lines.append(
+            f"| {r['layout']} | {r['B']} | {r['nstep_ms']:.4f} "
+            f"({r['nstep_min_ms']:.4f}-{r['nstep_max_ms']:.4f}) | "
+            f"{r['torch_ms']:.4f} "
+            f"({r['torch_min_ms']:.4f}-{r['torch_max_ms']:.4f}) | "
+            f"{r['onestep_ms']:.4f} "
+            f"({r['onestep_min_ms']:.4f}-{r['onestep_max_ms']:.4f}) | "
+            f"{r['nstep_GBps']:.0f} | "
+            f"{r['torch_ms'] / r['nstep_ms']:.2f}x | "
+            f"{r['nstep_ms'] / r['onestep_ms']:.3f} |"
+        )
+    lines.append("")
+    for L in (100, 1000):
+        stacked_b, dedup_b = stored_bytes(L)
+        lines.append(
+            f"RAINBOW frame bytes per stored transition, episodes of {L} "
+            f"steps: host fold into stacked rings {stacked_b}, raw "
+            f"episodes in the frame ring {dedup_b + 8:.0f} with the two "
+            f"int64 columns ({stacked_b / (dedup_b + 8):.2f}x)."
+        )
+    return lines
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--frames", type=int, default=65536,
@@ -68,11 +167,20 @@ def main():
     parser.add_argument("--iters", type=int, default=1000)
     parser.add_argument("--rounds", type=int, default=7)
     parser.add_argument("--out", default=None)
+    parser.add_argument("--n-step", type=int, default=1,
+                        help="> 1: time ops.framestack_gather_nstep")
     args = parser.parse_args()
     if not t.cuda.is_available():
         raise SystemExit("bench_framestack needs a GPU")
     dev = t.device("cuda:0")
     t.manual_seed(0)
+    if args.n_step > 1:
+        table = "\n".join(nstep_table(args, dev))
+        print(table)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(table + "\n")
+        return
 
     P, N = args.frames, args.transitions
     ring = t.randint(0, 256, (P, H, W), dtype=t.uint8, device=dev)
