@@ -13,10 +13,19 @@ n-step fold and skips its own per-transition host fold.
 ring slots. The buffer's `n_step` and `discount` must equal RAINBOW's
 `reward_future_steps` and `discount`.
 
-Runs on CPU too (the buffer falls back to torch ops), just slower; on
-an MI355X pass --device cuda:0.
+`--fused-loss` computes the whole C51 loss head (double-DQN action,
+projection, cross entropy and their backward) with `ops.c51_loss`, one
+gfx950 kernel each way, and bootstraps every sample with
+`discount ** m` for the `m` steps its window really covers
+(`exact_nstep_bootstrap`). `--logits` (implies `--fused-loss`) makes the
+net return logits; the loss then takes `log_softmax` in fp32 inside the
+kernel.
+
+Runs on CPU too (the buffer and the loss fall back to torch ops), just
+slower; on an MI355X pass --device cuda:0.
 
     python examples/rainbow_pixelcatch_framestack_replay.py [--device cuda:0]
+        [--fused-loss] [--logits]
 """
 import argparse
 import os
@@ -38,17 +47,20 @@ N_STEP, DISCOUNT, ATOMS = 3, 0.99, 51
 
 
 class DistQNet(nn.Module):
-    """C51 head on the Nature CNN: [B, actions, atoms] probabilities."""
+    """C51 head on the Nature CNN: [B, actions, atoms] probabilities,
+    or logits with ``logits=True``."""
 
-    def __init__(self, action_num=3, atom_num=ATOMS):
+    def __init__(self, action_num=3, atom_num=ATOMS, logits=False):
         super().__init__()
         self.action_num, self.atom_num = action_num, atom_num
+        self.logits = logits
         self.cnn = NatureCNN(4, feature_dim=256)
         self.head = nn.Linear(256, action_num * atom_num)
 
     def forward(self, state):
         a = self.head(self.cnn(state.float() / 255.0))
-        return t.softmax(a.view(-1, self.action_num, self.atom_num), dim=-1)
+        a = a.view(-1, self.action_num, self.atom_num)
+        return a if self.logits else t.softmax(a, dim=-1)
 
 
 def main():
@@ -56,12 +68,18 @@ def main():
     parser.add_argument("--device", default="cpu")
     parser.add_argument("--episodes", type=int, default=30)
     parser.add_argument("--replay-frames", type=int, default=20000)
+    parser.add_argument("--fused-loss", action="store_true",
+                        help="ops.c51_loss with discount ** m bootstrap")
+    parser.add_argument("--logits", action="store_true",
+                        help="the net returns logits (implies --fused-loss)")
     args = parser.parse_args()
     dev = t.device(args.device)
+    fused = args.fused_loss or args.logits
 
     t.manual_seed(0)
     rainbow = RAINBOW(
-        DistQNet().to(dev), DistQNet().to(dev), t.optim.Adam, -5.0, 5.0,
+        DistQNet(logits=args.logits).to(dev),
+        DistQNet(logits=args.logits).to(dev), t.optim.Adam, -5.0, 5.0,
         batch_size=32,
         reward_future_steps=N_STEP,
         discount=DISCOUNT,
@@ -72,9 +90,14 @@ def main():
             prioritized=True, n_step=N_STEP, discount=DISCOUNT,
         ),
         epsilon_decay=0.999,
+        fused_loss=fused,
+        exact_nstep_bootstrap=fused,
+        dist_from_logits=args.logits,
     )
     print("replay buffer:", type(rainbow.replay_buffer).__name__,
-          "n_step", rainbow.replay_buffer.n_step)
+          "n_step", rainbow.replay_buffer.n_step,
+          "fused loss", rainbow.fused_loss,
+          "logits", rainbow.dist_from_logits)
 
     env = PixelCatchEnv(seed=0, balls=3)
     for ep in range(args.episodes):

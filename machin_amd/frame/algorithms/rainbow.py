@@ -8,7 +8,17 @@ machin_amd.ops.categorical_projection on GPU), cross-entropy loss
 weighted by IS weights, abs-TD-style priority write-back.
 
 Model contract: ``qnet(state) -> [batch, action_num, atom_num]``
-distribution (softmaxed over atoms).
+distribution (softmaxed over atoms), or the logits of it with
+``dist_from_logits=True``.
+
+``fused_loss=True`` computes everything between the three network
+forwards and ``backward()`` with :func:`machin_amd.ops.c51_loss` (one
+gfx950 kernel each way on ROCm) in place of the eager chain; same
+values. It is required by ``dist_from_logits`` and by
+``exact_nstep_bootstrap=True``, which bootstraps every sample with
+``discount ** m`` for the ``m`` steps its n-step window really covers
+(needs a replay buffer that returns ``m`` as the ``n_step`` attribute,
+i.e. ``DeviceFrameStackBuffer(n_step > 1)``).
 """
 from typing import Any, Dict, List, Union
 
@@ -37,8 +47,17 @@ class RAINBOW(DQNPer):
         replay_size: int = 500000,
         replay_device: Union[str, t.device] = "cpu",
         replay_buffer=None,
+        fused_loss: bool = False,
+        dist_from_logits: bool = False,
+        exact_nstep_bootstrap: bool = False,
         **kwargs,
     ):
+        if dist_from_logits and not fused_loss:
+            raise ValueError("dist_from_logits=True requires fused_loss=True.")
+        if exact_nstep_bootstrap and not fused_loss:
+            raise ValueError(
+                "exact_nstep_bootstrap=True requires fused_loss=True."
+            )
         super().__init__(
             qnet,
             qnet_target,
@@ -52,6 +71,9 @@ class RAINBOW(DQNPer):
         self.v_min = float(value_min)
         self.v_max = float(value_max)
         self.reward_future_steps = reward_future_steps
+        self.fused_loss = bool(fused_loss)
+        self.dist_from_logits = bool(dist_from_logits)
+        self.exact_nstep_bootstrap = bool(exact_nstep_bootstrap)
 
     # ------------------------------------------------------------------
     def _criticize(self, state: Dict[str, Any], use_target: bool = False,
@@ -62,6 +84,8 @@ class RAINBOW(DQNPer):
 
     def _q_values(self, dist: t.Tensor) -> t.Tensor:
         B, A, N = dist.shape
+        if self.dist_from_logits:
+            dist = t.softmax(dist.float(), dim=2)
         support = t.linspace(
             self.v_min, self.v_max, N, device=dist.device
         )
@@ -96,9 +120,12 @@ class RAINBOW(DQNPer):
         ``reward_future_steps`` and ``discount``. Sampled rows are then
         what the host fold stores, and ``update`` bootstraps every
         sample with ``discount ** reward_future_steps`` on both paths,
-        windows cut short by the episode's end included; the buffer
+        windows cut short by the episode's end included. The buffer
         also returns the per-sample step count ``m`` as the custom
-        attribute ``n_step`` for users who want ``discount ** m``.
+        attribute ``n_step``; with ``exact_nstep_bootstrap=True``
+        (needs ``fused_loss=True``) ``update`` bootstraps with
+        ``discount ** m`` instead, which differs for windows cut short
+        by a non-terminal episode end (a time limit).
         """
         buffer_n = getattr(self.replay_buffer, "n_step", 1)
         if buffer_n > 1:
@@ -155,6 +182,24 @@ class RAINBOW(DQNPer):
         )
 
     # ------------------------------------------------------------------
+    def _bootstrap_discount(self, others, device):
+        """Discount of the bootstrap term for the fused loss: the scalar
+        ``discount ** reward_future_steps``, or with
+        ``exact_nstep_bootstrap`` the f32 ``[B]`` tensor
+        ``discount ** m`` from the sampled ``n_step`` attribute."""
+        if not self.exact_nstep_bootstrap:
+            return self.discount ** self.reward_future_steps
+        steps = others.get("n_step") if isinstance(others, dict) else None
+        if not t.is_tensor(steps):
+            raise ValueError(
+                "exact_nstep_bootstrap=True needs the per-sample step "
+                "count as the sampled attribute 'n_step'; a "
+                "DeviceFrameStackBuffer(n_step > 1) provides it, "
+                f"{type(self.replay_buffer).__name__} did not."
+            )
+        steps = steps.to(device=device, dtype=t.float32).view(-1)
+        return t.pow(float(self.discount), steps)
+
     def update(self, update_value=True, update_target=True,
                concatenate_samples=True, **__):
         (
@@ -176,23 +221,40 @@ class RAINBOW(DQNPer):
         device = dist.device
         action_index = action["action"].to(device=device, dtype=t.long).view(B)
 
-        with t.no_grad():
-            # double-DQN action selection with the online net
-            online_next = self._criticize(next_state)
-            next_q = self._q_values(online_next)
-            best = next_q.argmax(dim=1)  # [B]
-            target_next = self._criticize(next_state, use_target=True)
-            next_dist = target_next[t.arange(B, device=device), best]  # [B,N]
-            reward = reward.to(device).float().view(B)
-            terminal = terminal.to(device).float().view(B)
-            gamma_n = self.discount ** self.reward_future_steps
-            proj = ops.categorical_projection(
-                next_dist, reward, terminal, gamma_n, self.v_min, self.v_max
+        if self.fused_loss:
+            # action selection, gather, projection and cross entropy in
+            # one op (one kernel each way on ROCm)
+            with t.no_grad():
+                online_next = self._criticize(next_state)
+                target_next = self._criticize(next_state, use_target=True)
+            per_sample, _, _ = ops.c51_loss(
+                dist, action_index, online_next, target_next,
+                reward.to(device), terminal.to(device),
+                self._bootstrap_discount(others, device),
+                self.v_min, self.v_max,
+                from_logits=self.dist_from_logits,
             )
+        else:
+            with t.no_grad():
+                # double-DQN action selection with the online net
+                online_next = self._criticize(next_state)
+                next_q = self._q_values(online_next)
+                best = next_q.argmax(dim=1)  # [B]
+                target_next = self._criticize(next_state, use_target=True)
+                next_dist = target_next[
+                    t.arange(B, device=device), best
+                ]  # [B,N]
+                reward = reward.to(device).float().view(B)
+                terminal = terminal.to(device).float().view(B)
+                gamma_n = self.discount ** self.reward_future_steps
+                proj = ops.categorical_projection(
+                    next_dist, reward, terminal, gamma_n, self.v_min,
+                    self.v_max
+                )
 
-        pred = dist[t.arange(B, device=device), action_index]  # [B,N]
-        log_pred = t.log(pred.clamp_min(1e-8))
-        per_sample = -(proj * log_pred).sum(dim=1)  # cross entropy
+            pred = dist[t.arange(B, device=device), action_index]  # [B,N]
+            log_pred = t.log(pred.clamp_min(1e-8))
+            per_sample = -(proj * log_pred).sum(dim=1)  # cross entropy
         weights = t.as_tensor(
             is_weight, dtype=per_sample.dtype, device=device
         ).view(B)

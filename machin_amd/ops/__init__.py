@@ -478,6 +478,201 @@ def categorical_projection(
     return proj
 
 
+def _c51_loss_check(dist, action, next_online, next_target, reward,
+                    terminal, discount, v_min, v_max):
+    """Shared argument validation of :func:`c51_loss`; returns
+    ``(action [B], reward [B], terminal [B], discount float or [B])``."""
+    if dist.dim() != 3:
+        raise ValueError("dist must be [B, A, N]")
+    B, A, N = dist.shape
+    for name, x in (("next_online", next_online),
+                    ("next_target", next_target)):
+        if x.shape != dist.shape or x.dtype != dist.dtype:
+            raise ValueError(
+                f"{name} must have dist's shape and dtype"
+            )
+    if not 2 <= N <= 256:
+        raise ValueError("atoms must be in [2, 256]")
+    if not 1 <= A <= 64:
+        raise ValueError("actions must be in [1, 64]")
+    if not float(v_min) < float(v_max):
+        raise ValueError("v_min must be below v_max")
+    if action.dtype != t.int64 or action.numel() != B:
+        raise ValueError("action must be int64 [B] or [B, 1]")
+    if reward.numel() != B or terminal.numel() != B:
+        raise ValueError("reward and terminal must have B elements")
+    if t.is_tensor(discount):
+        if discount.dtype != t.float32 or discount.numel() != B:
+            raise ValueError("a tensor discount must be float32 [B]")
+        discount = discount.detach().reshape(B)
+    else:
+        discount = float(discount)
+    for name, x in (("action", action), ("next_online", next_online),
+                    ("next_target", next_target), ("reward", reward),
+                    ("terminal", terminal), ("discount", discount)):
+        if t.is_tensor(x) and x.device != dist.device:
+            raise ValueError(f"{name} must be on dist's device")
+    return (
+        action.reshape(B),
+        reward.detach().float().reshape(B),
+        terminal.detach().float().reshape(B),
+        discount,
+    )
+
+
+def _c51_loss_torch(
+    dist: t.Tensor, action: t.Tensor, next_online: t.Tensor,
+    next_target: t.Tensor, reward: t.Tensor, terminal: t.Tensor,
+    discount, v_min: float, v_max: float, from_logits: bool = False,
+):
+    """Torch composition of :func:`c51_loss` (the CPU path and the
+    reference the kernel is tested and timed against). Differentiable
+    with respect to ``dist``. Computes in fp32; float64 inputs are
+    accepted here (not by the kernel) and computed in float64, for
+    gradient checks."""
+    if dist.dtype not in (t.float32, t.bfloat16, t.float64):
+        raise ValueError("dist must be float32 or bfloat16")
+    action, reward, terminal, discount = _c51_loss_check(
+        dist, action, next_online, next_target, reward, terminal,
+        discount, v_min, v_max,
+    )
+    B, A, N = dist.shape
+    dev = dist.device
+    ct = t.float64 if dist.dtype == t.float64 else t.float32
+    rows = t.arange(B, device=dev)
+
+    def prob(x):
+        x = x.to(ct)
+        return t.softmax(x, dim=-1) if from_logits else x
+
+    with t.no_grad():
+        v_min, v_max = float(v_min), float(v_max)
+        z = t.linspace(v_min, v_max, N, device=dev, dtype=ct)
+        q = (prob(next_online) * z.view(1, 1, N)).sum(dim=2)
+        best = q.argmax(dim=1)
+        nd = prob(next_target)[rows, best]
+        if not t.is_tensor(discount):
+            discount = t.full((B,), discount, device=dev, dtype=ct)
+        gamma = discount.to(device=dev, dtype=ct).view(B, 1)
+        alive = 1.0 - terminal.to(ct).view(B, 1)
+        delta_z = (v_max - v_min) / (N - 1)
+        tz = (reward.to(ct).view(B, 1) + gamma * alive * z.view(1, N)).clamp(
+            v_min, v_max
+        )
+        pos = (tz - v_min) / delta_z
+        lo_f, hi_f = pos.floor(), pos.ceil()
+        # when pos is integral, all mass goes to lo
+        w_lo = t.where(lo_f == hi_f, t.ones_like(pos), hi_f - pos)
+        w_hi = pos - lo_f
+        lo = lo_f.long().clamp(0, N - 1)
+        hi = hi_f.long().clamp(0, N - 1)
+        proj = t.zeros_like(nd)
+        offset = (rows * N).view(B, 1)
+        proj.view(-1).index_add_(0, (lo + offset).view(-1),
+                                 (nd * w_lo).view(-1))
+        proj.view(-1).index_add_(0, (hi + offset).view(-1),
+                                 (nd * w_hi).view(-1))
+    pred = dist[rows, action.clamp(0, A - 1)].to(ct)
+    if from_logits:
+        log_pred = t.log_softmax(pred, dim=-1)
+    else:
+        log_pred = t.log(pred.clamp_min(1e-8))
+    loss = -(proj * log_pred).sum(dim=1)
+    return loss, proj, best
+
+
+class _C51Loss(t.autograd.Function):
+    @staticmethod
+    def forward(ctx, dist, action, next_online, next_target, reward,
+                terminal, discount, v_min, v_max, from_logits):
+        ext = _require_ext()
+        dist = dist.contiguous()
+        tensor_discount = t.is_tensor(discount)
+        loss, proj, best, lse, s_sum = ext.c51_loss_fwd(
+            dist, action, next_online.contiguous(),
+            next_target.contiguous(), reward, terminal,
+            discount.contiguous() if tensor_discount else None,
+            0.0 if tensor_discount else discount,
+            v_min, v_max, from_logits,
+        )
+        ctx.save_for_backward(dist, action, proj, lse, s_sum)
+        ctx.from_logits = from_logits
+        ctx.mark_non_differentiable(proj, best)
+        return loss, proj, best
+
+    @staticmethod
+    def backward(ctx, g_loss, g_proj, g_best):
+        dist, action, proj, lse, s_sum = ctx.saved_tensors
+        grad = _require_ext().c51_loss_bwd(
+            dist, action, proj, lse, s_sum, g_loss.contiguous().float(),
+            ctx.from_logits,
+        )
+        return (grad,) + (None,) * 9
+
+
+def c51_loss(
+    dist: t.Tensor, action: t.Tensor, next_online: t.Tensor,
+    next_target: t.Tensor, reward: t.Tensor, terminal: t.Tensor,
+    discount, v_min: float, v_max: float, from_logits: bool = False,
+):
+    """Fused C51 (categorical DQN) loss head with double-DQN action
+    selection and a per-sample discount: returns ``(loss [B], proj
+    [B, N], best [B])``.
+
+    ``dist``, ``next_online`` and ``next_target`` are ``[B, A, N]``
+    (batch, actions, atoms), all fp32 or all bf16: the online net on
+    the sampled states, the online net and the target net on the next
+    states. ``action`` is int64 ``[B]`` or ``[B, 1]``, ``reward`` and
+    ``terminal`` hold ``B`` elements (cast to fp32) and ``discount`` is
+    a float or an fp32 ``[B]`` tensor, e.g. ``gamma ** m`` for n-step
+    windows of ``m`` steps. Limits: ``2 <= N <= 256``,
+    ``1 <= A <= 64``, ``v_min < v_max``.
+
+    With ``dz = (v_max - v_min) / (N - 1)``, ``z_i = v_min + i dz`` and
+    ``P(x)`` either ``x`` (``from_logits=False``, the inputs are
+    probabilities) or the softmax over atoms (``from_logits=True``),
+    all in fp32::
+
+        q[b, a]  = sum_i P(next_online)[b, a, i] z_i
+        best[b]  = lowest a with maximal q[b, a]
+        nd[b]    = P(next_target)[b, best[b]]
+        proj[b]  = nd[b] projected onto the support under
+                   tz_i = clamp(reward_b + discount_b (1 - terminal_b) z_i,
+                                v_min, v_max)
+                   (:func:`categorical_projection` with a per-row
+                   discount; bin indices are clamped to [0, N-1])
+        a_b      = clamp(action[b], 0, A - 1)
+        loss[b]  = -sum_i proj[b, i] log(max(dist[b, a_b, i], 1e-8))
+                or -sum_i proj[b, i] log_softmax(dist[b, a_b])_i
+
+    ``loss`` is differentiable with respect to ``dist`` only (``-g proj
+    / dist`` where ``dist >= 1e-8``, or ``g (softmax(dist) sum(proj) -
+    proj)`` for logits; rows of other actions get zero); ``proj`` and
+    ``best`` (int64) are detached.
+
+    On ROCm this is one gfx950 kernel forward and one backward
+    (machin_amd/ops/hip/c51_loss.hip); the CPU fallback is the same
+    semantics as a torch composition.
+    """
+    from_logits = bool(from_logits)
+    if not dist.is_cuda:
+        return _c51_loss_torch(
+            dist, action, next_online, next_target, reward, terminal,
+            discount, v_min, v_max, from_logits,
+        )
+    if dist.dtype not in (t.float32, t.bfloat16):
+        raise ValueError("dist must be float32 or bfloat16")
+    action, reward, terminal, discount = _c51_loss_check(
+        dist, action, next_online, next_target, reward, terminal,
+        discount, v_min, v_max,
+    )
+    return _C51Loss.apply(
+        dist, action.contiguous(), next_online.detach(),
+        next_target.detach(), reward.contiguous(), terminal.contiguous(),
+        discount, float(v_min), float(v_max), from_logits,
+    )
+
+
 class _PGHead(t.autograd.Function):
     @staticmethod
     def forward(ctx, logits, actions):
@@ -714,6 +909,7 @@ __all__ = [
     "vtrace",
     "categorical_projection",
     "categorical_policy_head",
+    "c51_loss",
     "FusedPolyak",
     "FusedRMSprop",
 ]

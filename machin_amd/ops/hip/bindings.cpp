@@ -33,6 +33,14 @@ void vtrace_bt_launch(const float*, const float*, const float*,
 void categorical_projection_launch(const float*, const float*, const float*,
                                    float*, int64_t, int64_t, float, float,
                                    float, hipStream_t);
+void c51_loss_fwd_launch(const void*, const int64_t*, const void*,
+                         const void*, const float*, const float*,
+                         const float*, float, float*, float*, int64_t*,
+                         float*, float*, int64_t, int, int, float, float,
+                         bool, bool, hipStream_t);
+void c51_loss_bwd_launch(const void*, const int64_t*, const float*,
+                         const float*, const float*, const float*, void*,
+                         int64_t, int, int, bool, bool, hipStream_t);
 void multi_tensor_polyak_launch(void*, const int64_t*, int64_t, int64_t,
                                 float, hipStream_t);
 void fused_rmsprop_launch(void*, const int64_t*, int64_t, int64_t,
@@ -225,6 +233,101 @@ Tensor categorical_projection(Tensor next_dist, Tensor rew, Tensor nd,
                                 (float)v_min, (float)v_max,
                                 current_stream());
   return out;
+}
+
+// ------------------------------------------------------------------
+// fused C51 loss head (semantics: machin_amd.ops.c51_loss)
+// ------------------------------------------------------------------
+void check_c51_dist(const Tensor& t, const Tensor& like, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 3, name,
+              " must be a contiguous [B, A, N] CUDA tensor");
+  TORCH_CHECK(t.scalar_type() == like.scalar_type() &&
+                  t.sizes() == like.sizes() && t.device() == like.device(),
+              name, " must match dist in dtype, shape and device");
+}
+
+void check_c51_rows(const Tensor& t, const Tensor& dist, at::ScalarType dt,
+                    const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dist.device() &&
+                  t.scalar_type() == dt && t.is_contiguous() &&
+                  t.dim() == 1 && t.size(0) == dist.size(0),
+              name, " must be a contiguous [B] ", dt,
+              " tensor on dist's device");
+}
+
+// Returns {loss [B], proj [B, N], best [B] int64, lse [B], S [B]}.
+// An undefined `discount` means the scalar one for every row.
+std::vector<Tensor> c51_loss_fwd(Tensor dist, Tensor action,
+                                 Tensor next_online, Tensor next_target,
+                                 Tensor reward, Tensor terminal,
+                                 c10::optional<Tensor> discount,
+                                 double discount_scalar, double v_min,
+                                 double v_max, bool from_logits) {
+  TORCH_CHECK(dist.scalar_type() == at::kFloat ||
+                  dist.scalar_type() == at::kBFloat16,
+              "dist must be float32 or bfloat16");
+  check_c51_dist(dist, dist, "dist");
+  check_c51_dist(next_online, dist, "next_online");
+  check_c51_dist(next_target, dist, "next_target");
+  const int64_t B = dist.size(0), A = dist.size(1), N = dist.size(2);
+  TORCH_CHECK(N >= 2 && N <= 256, "atoms must be in [2, 256]");
+  TORCH_CHECK(A >= 1 && A <= 64, "actions must be in [1, 64]");
+  TORCH_CHECK(v_min < v_max, "v_min must be below v_max");
+  check_c51_rows(action, dist, at::kLong, "action");
+  check_c51_rows(reward, dist, at::kFloat, "reward");
+  check_c51_rows(terminal, dist, at::kFloat, "terminal");
+  const float* discount_ptr = nullptr;
+  if (discount.has_value() && discount->defined()) {
+    check_c51_rows(*discount, dist, at::kFloat, "discount");
+    discount_ptr = discount->data_ptr<float>();
+  }
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dist.device());
+  const auto f32 = dist.options().dtype(at::kFloat);
+  Tensor loss = at::empty({B}, f32);
+  Tensor proj = at::empty({B, N}, f32);
+  Tensor best = at::empty({B}, dist.options().dtype(at::kLong));
+  Tensor lse = at::empty({B}, f32);
+  Tensor s_sum = at::empty({B}, f32);
+  c51_loss_fwd_launch(
+      dist.data_ptr(), action.data_ptr<int64_t>(), next_online.data_ptr(),
+      next_target.data_ptr(), reward.data_ptr<float>(),
+      terminal.data_ptr<float>(), discount_ptr, (float)discount_scalar,
+      loss.data_ptr<float>(), proj.data_ptr<float>(),
+      best.data_ptr<int64_t>(), lse.data_ptr<float>(),
+      s_sum.data_ptr<float>(), B, (int)A, (int)N, (float)v_min,
+      (float)v_max, dist.scalar_type() == at::kBFloat16, from_logits,
+      current_stream());
+  return {loss, proj, best, lse, s_sum};
+}
+
+// grad_dist in dist's dtype, every element written.
+Tensor c51_loss_bwd(Tensor dist, Tensor action, Tensor proj, Tensor lse,
+                    Tensor s_sum, Tensor g, bool from_logits) {
+  TORCH_CHECK(dist.scalar_type() == at::kFloat ||
+                  dist.scalar_type() == at::kBFloat16,
+              "dist must be float32 or bfloat16");
+  check_c51_dist(dist, dist, "dist");
+  const int64_t B = dist.size(0), A = dist.size(1), N = dist.size(2);
+  TORCH_CHECK(N >= 2 && N <= 256, "atoms must be in [2, 256]");
+  TORCH_CHECK(A >= 1 && A <= 64, "actions must be in [1, 64]");
+  check_c51_rows(action, dist, at::kLong, "action");
+  check_c51_rows(lse, dist, at::kFloat, "lse");
+  check_c51_rows(s_sum, dist, at::kFloat, "S");
+  check_c51_rows(g, dist, at::kFloat, "g");
+  TORCH_CHECK(proj.is_cuda() && proj.device() == dist.device() &&
+                  proj.scalar_type() == at::kFloat && proj.is_contiguous() &&
+                  proj.dim() == 2 && proj.size(0) == B && proj.size(1) == N,
+              "proj must be a contiguous [B, N] float32 tensor on dist's "
+              "device");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dist.device());
+  Tensor grad = at::empty_like(dist);
+  c51_loss_bwd_launch(dist.data_ptr(), action.data_ptr<int64_t>(),
+                      proj.data_ptr<float>(), lse.data_ptr<float>(),
+                      s_sum.data_ptr<float>(), g.data_ptr<float>(),
+                      grad.data_ptr(), B, (int)A, (int)N,
+                      dist.scalar_type() == at::kBFloat16, from_logits,
+                      current_stream());
+  return grad;
 }
 
 // ------------------------------------------------------------------
@@ -747,6 +850,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vtrace", &vtrace);
   m.def("vtrace_bt", &vtrace_bt);
   m.def("categorical_projection", &categorical_projection);
+  m.def("c51_loss_fwd", &c51_loss_fwd);
+  m.def("c51_loss_bwd", &c51_loss_bwd);
   m.def("multi_tensor_polyak", &multi_tensor_polyak);
   m.def("multi_tensor_polyak_cached", &multi_tensor_polyak_cached);
   m.def("fused_rmsprop_cached", &fused_rmsprop_cached);

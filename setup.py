@@ -24,6 +24,7 @@ SOURCES = [
     "sumtree.hip",
     "scans.hip",
     "projection.hip",
+    "c51_loss.hip",
     "multi_tensor.hip",
     "distributions.hip",
     "elementwise.hip",
