@@ -449,6 +449,11 @@ def categorical_projection(
 ) -> t.Tensor:
     """Project r + gamma*(1-d)*z onto the fixed support; [B, A] -> [B, A].
 
+    ``2 <= A <= 256``. Positions are computed in fp32 and bin indices
+    are clamped to ``[0, A-1]`` (for some supports the fp32 position of
+    ``v_max`` rounds to just above ``A-1``), so every row keeps its
+    mass.
+
     Reference semantics: machin/frame/algorithms/rainbow.py:221-301.
     """
     B, A = next_dist.shape
@@ -465,12 +470,14 @@ def categorical_projection(
     z = t.linspace(v_min, v_max, A, device=next_dist.device)
     tz = (rewards + gamma * nd * z.view(1, A)).clamp(v_min, v_max)
     b = (tz - v_min) / delta_z
-    lo = b.floor().long()
-    hi = b.ceil().long()
+    lo_f, hi_f = b.floor(), b.ceil()
     # when b is integral, put all mass on lo
-    same = lo == hi
-    w_lo = t.where(same, t.ones_like(b), hi.float() - b)
-    w_hi = b - lo.float()
+    w_lo = t.where(lo_f == hi_f, t.ones_like(b), hi_f - b)
+    w_hi = b - lo_f
+    # fp32 (v_max - v_min) / delta_z can round to just above A-1, so
+    # the bins are clamped to the support (as in _c51_loss_torch)
+    lo = lo_f.long().clamp(0, A - 1)
+    hi = hi_f.long().clamp(0, A - 1)
     proj = t.zeros_like(next_dist)
     offset = (t.arange(B, device=next_dist.device) * A).view(B, 1)
     proj.view(-1).index_add_(0, (lo + offset).view(-1), (next_dist * w_lo).view(-1))

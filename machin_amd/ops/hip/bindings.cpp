@@ -102,6 +102,38 @@ void check_f32_cuda(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// Every further tensor argument of an op: on `ref`'s device, of dtype
+// `dt`, contiguous and holding exactly `numel` elements. Runs before
+// the launch, so a kernel never indexes a short or foreign buffer.
+void check_arg(const Tensor& t, const Tensor& ref, at::ScalarType dt,
+               int64_t numel, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), name,
+              " must be a CUDA tensor on the first argument's device");
+  TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt);
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.numel() == numel, name, " must hold ", numel,
+              " elements, got ", t.numel());
+}
+
+// [rows, cols] float32 first argument of the scans and heads
+void check_f32_2d(const Tensor& t, const char* name) {
+  check_f32_cuda(t, name);
+  TORCH_CHECK(t.dim() == 2, name, " must be 2-D");
+}
+
+// tree [2 * capacity] float32 with capacity == 2^depth
+void check_tree(const Tensor& tree, int64_t capacity, int64_t depth) {
+  check_f32_cuda(tree, "tree");
+  TORCH_CHECK(depth >= 1 && depth < 62 &&
+                  capacity == ((int64_t)1 << depth),
+              "capacity must be 2^depth with depth >= 1");
+  TORCH_CHECK(tree.numel() == 2 * capacity,
+              "tree must hold 2 * capacity elements");
+  // the sampling walk loads the two children of a node as one float2
+  TORCH_CHECK((uintptr_t)tree.data_ptr() % 8 == 0,
+              "tree must be 8-byte aligned");
+}
+
 hipStream_t current_stream() {
   return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
 }
@@ -111,11 +143,9 @@ hipStream_t current_stream() {
 // ------------------------------------------------------------------
 void sumtree_update(Tensor tree, Tensor idx, Tensor w, int64_t capacity,
                     int64_t depth) {
-  check_f32_cuda(tree, "tree");
-  check_f32_cuda(w, "w");
-  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kLong &&
-                  idx.is_contiguous(),
-              "idx must be contiguous int64 CUDA");
+  check_tree(tree, capacity, depth);
+  check_arg(idx, tree, at::kLong, idx.numel(), "idx");
+  check_arg(w, tree, at::kFloat, idx.numel(), "w");
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(tree.device());
   sumtree_update_launch(tree.data_ptr<float>(), idx.data_ptr<int64_t>(),
                         w.data_ptr<float>(), idx.numel(), capacity,
@@ -124,14 +154,20 @@ void sumtree_update(Tensor tree, Tensor idx, Tensor w, int64_t capacity,
 
 void sumtree_build(Tensor tree, int64_t capacity) {
   check_f32_cuda(tree, "tree");
+  TORCH_CHECK(capacity >= 2 && (capacity & (capacity - 1)) == 0 &&
+                  tree.numel() == 2 * capacity,
+              "tree must hold 2 * capacity elements, capacity a power of "
+              "two >= 2");
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(tree.device());
   sumtree_build_launch(tree.data_ptr<float>(), capacity, current_stream());
 }
 
 Tensor sumtree_sample(Tensor tree, Tensor u, int64_t capacity, int64_t depth,
                       int64_t size) {
-  check_f32_cuda(tree, "tree");
-  check_f32_cuda(u, "u");
+  check_tree(tree, capacity, depth);
+  check_arg(u, tree, at::kFloat, u.numel(), "u");
+  TORCH_CHECK(size >= 1 && size <= capacity,
+              "size must be in [1, capacity]");
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(tree.device());
   Tensor out = at::empty({u.numel()}, u.options().dtype(at::kLong));
   sumtree_sample_launch(tree.data_ptr<float>(), u.data_ptr<float>(),
@@ -145,9 +181,11 @@ Tensor sumtree_sample(Tensor tree, Tensor u, int64_t capacity, int64_t depth,
 // ------------------------------------------------------------------
 Tensor discounted_returns(Tensor rew, Tensor nd, Tensor bootstrap,
                           double gamma) {
-  check_f32_cuda(rew, "rewards");
-  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
+  check_f32_2d(rew, "rewards");
   int64_t T = rew.size(0), B = rew.size(1);
+  check_arg(nd, rew, at::kFloat, T * B, "non-terminal mask");
+  check_arg(bootstrap, rew, at::kFloat, B, "bootstrap");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
   Tensor out = at::empty_like(rew);
   discounted_returns_launch(rew.data_ptr<float>(), nd.data_ptr<float>(),
                             bootstrap.data_ptr<float>(),
@@ -158,9 +196,12 @@ Tensor discounted_returns(Tensor rew, Tensor nd, Tensor bootstrap,
 
 Tensor gae(Tensor rew, Tensor val, Tensor next_val, Tensor nd, double gamma,
            double lam) {
-  check_f32_cuda(rew, "rewards");
-  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
+  check_f32_2d(rew, "rewards");
   int64_t T = rew.size(0), B = rew.size(1);
+  check_arg(val, rew, at::kFloat, T * B, "values");
+  check_arg(next_val, rew, at::kFloat, T * B, "next_values");
+  check_arg(nd, rew, at::kFloat, T * B, "non-terminal mask");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
   Tensor out = at::empty_like(rew);
   gae_launch(rew.data_ptr<float>(), val.data_ptr<float>(),
              next_val.data_ptr<float>(), nd.data_ptr<float>(),
@@ -173,9 +214,14 @@ std::vector<Tensor> vtrace(Tensor blp, Tensor tlp, Tensor rew, Tensor val,
                            Tensor bootstrap, Tensor nd, double gamma,
                            double rho_clip, double c_clip,
                            double pg_rho_clip) {
-  check_f32_cuda(rew, "rewards");
-  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
+  check_f32_2d(rew, "rewards");
   int64_t T = rew.size(0), B = rew.size(1);
+  check_arg(blp, rew, at::kFloat, T * B, "behavior_log_probs");
+  check_arg(tlp, rew, at::kFloat, T * B, "target_log_probs");
+  check_arg(val, rew, at::kFloat, T * B, "values");
+  check_arg(nd, rew, at::kFloat, T * B, "non-terminal mask");
+  check_arg(bootstrap, rew, at::kFloat, B, "bootstrap_value");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
   Tensor vs = at::empty_like(rew);
   Tensor pg_adv = at::empty_like(rew);
   vtrace_launch(blp.data_ptr<float>(), tlp.data_ptr<float>(),
@@ -191,9 +237,14 @@ std::vector<Tensor> vtrace_bt(Tensor blp, Tensor tlp, Tensor rew,
                               Tensor val, Tensor bootstrap, Tensor nd,
                               double gamma, double rho_clip,
                               double c_clip, double pg_rho_clip) {
-  check_f32_cuda(rew, "rewards");
-  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
+  check_f32_2d(rew, "rewards");
   int64_t B = rew.size(0), T = rew.size(1);
+  check_arg(blp, rew, at::kFloat, T * B, "behavior_log_probs");
+  check_arg(tlp, rew, at::kFloat, T * B, "target_log_probs");
+  check_arg(val, rew, at::kFloat, T * B, "values");
+  check_arg(nd, rew, at::kFloat, T * B, "non-terminal mask");
+  check_arg(bootstrap, rew, at::kFloat, B, "bootstrap_value");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
   Tensor vs = at::empty_like(rew);
   Tensor pg_adv = at::empty_like(rew);
   vtrace_bt_launch(blp.data_ptr<float>(), tlp.data_ptr<float>(),
@@ -206,10 +257,10 @@ std::vector<Tensor> vtrace_bt(Tensor blp, Tensor tlp, Tensor rew,
 }
 
 Tensor nstep_returns(Tensor rew, Tensor alive, double gamma, int64_t n) {
-  check_f32_cuda(rew, "rewards");
-  check_f32_cuda(alive, "alive");
-  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
+  check_f32_2d(rew, "rewards");
   int64_t T = rew.size(0), B = rew.size(1);
+  check_arg(alive, rew, at::kFloat, T * B, "alive");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rew.device());
   Tensor out = at::empty_like(rew);
   nstep_returns_launch(rew.data_ptr<float>(), alive.data_ptr<float>(),
                        out.data_ptr<float>(), T, B, (float)gamma, (int)n,
@@ -222,10 +273,13 @@ Tensor nstep_returns(Tensor rew, Tensor alive, double gamma, int64_t n) {
 // ------------------------------------------------------------------
 Tensor categorical_projection(Tensor next_dist, Tensor rew, Tensor nd,
                               double gamma, double v_min, double v_max) {
-  check_f32_cuda(next_dist, "next_dist");
-  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(next_dist.device());
+  check_f32_2d(next_dist, "next_dist");
   int64_t B = next_dist.size(0), A = next_dist.size(1);
-  TORCH_CHECK(A <= 256, "categorical projection supports at most 256 atoms");
+  TORCH_CHECK(A >= 2 && A <= 256,
+              "categorical projection supports 2 to 256 atoms");
+  check_arg(rew, next_dist, at::kFloat, B, "rewards");
+  check_arg(nd, next_dist, at::kFloat, B, "non-terminal mask");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(next_dist.device());
   Tensor out = at::empty_like(next_dist);
   categorical_projection_launch(next_dist.data_ptr<float>(),
                                 rew.data_ptr<float>(), nd.data_ptr<float>(),
@@ -405,10 +459,10 @@ std::vector<Tensor> gaussian_sample_logprob(Tensor mu, Tensor log_std,
                                             int64_t seed, int64_t offset,
                                             bool tanh_squash,
                                             double epsilon) {
-  check_f32_cuda(mu, "mu");
-  check_f32_cuda(log_std, "log_std");
-  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(mu.device());
+  check_f32_2d(mu, "mu");
   int64_t B = mu.size(0), D = mu.size(1);
+  check_arg(log_std, mu, at::kFloat, B * D, "log_std");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(mu.device());
   Tensor act = at::empty_like(mu);
   Tensor logp = at::empty({B, 1}, mu.options());
   gaussian_sample_logprob_launch(
@@ -420,9 +474,11 @@ std::vector<Tensor> gaussian_sample_logprob(Tensor mu, Tensor log_std,
 
 Tensor gaussian_logprob(Tensor mu, Tensor log_std, Tensor act,
                         bool tanh_squash, double epsilon) {
-  check_f32_cuda(mu, "mu");
-  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(mu.device());
+  check_f32_2d(mu, "mu");
   int64_t B = mu.size(0), D = mu.size(1);
+  check_arg(log_std, mu, at::kFloat, B * D, "log_std");
+  check_arg(act, mu, at::kFloat, B * D, "act");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(mu.device());
   Tensor logp = at::empty({B, 1}, mu.options());
   gaussian_logprob_launch(mu.data_ptr<float>(), log_std.data_ptr<float>(),
                           act.data_ptr<float>(), logp.data_ptr<float>(), B,
@@ -453,10 +509,10 @@ std::vector<Tensor> pg_head_fwd(Tensor logits, Tensor actions) {
   TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16 &&
                   logits.is_contiguous(),
               "logits must be contiguous bf16 CUDA [N, A]");
-  TORCH_CHECK(actions.scalar_type() == at::kLong && actions.is_contiguous(),
-              "actions must be contiguous int64");
+  TORCH_CHECK(logits.dim() == 2, "logits must be 2-D");
   int64_t N = logits.size(0), A = logits.size(1);
-  TORCH_CHECK(A <= 32, "pg_head supports at most 32 actions");
+  TORCH_CHECK(A >= 1 && A <= 32, "pg_head supports 1 to 32 actions");
+  check_arg(actions, logits, at::kLong, N, "actions");
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
   Tensor tl = at::empty({N}, logits.options().dtype(at::kFloat));
   Tensor ent = at::empty({N}, logits.options().dtype(at::kFloat));
@@ -468,9 +524,14 @@ std::vector<Tensor> pg_head_fwd(Tensor logits, Tensor actions) {
 
 Tensor pg_head_bwd(Tensor logits, Tensor actions, Tensor g_taken,
                    Tensor g_ent) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16 &&
+                  logits.is_contiguous() && logits.dim() == 2,
+              "logits must be contiguous bf16 CUDA [N, A]");
   int64_t N = logits.size(0), A = logits.size(1);
-  check_f32_cuda(g_taken, "g_taken");
-  check_f32_cuda(g_ent, "g_ent");
+  TORCH_CHECK(A >= 1 && A <= 32, "pg_head supports 1 to 32 actions");
+  check_arg(actions, logits, at::kLong, N, "actions");
+  check_arg(g_taken, logits, at::kFloat, N, "g_taken");
+  check_arg(g_ent, logits, at::kFloat, N, "g_ent");
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
   Tensor d = at::empty_like(logits);
   pg_head_bwd_launch(logits.data_ptr(), actions.data_ptr<int64_t>(),

@@ -57,6 +57,16 @@ __global__ void u8_to_bf16_scale_tail_kernel(
 void u8_to_bf16_scale_launch(const unsigned char* in, void* out, int64_t n,
                              float scale, hipStream_t stream) {
   const int block = 256;
+  if (n <= 0) return;
+  if ((uintptr_t)in % 16 != 0 || (uintptr_t)out % 16 != 0) {
+    // a slice such as x[1:] starts off a 16-byte boundary: the vector
+    // kernel's uint4 accesses need alignment, so the scalar kernel
+    // takes the whole range
+    hipLaunchKernelGGL(u8_to_bf16_scale_tail_kernel,
+                       dim3(ma_grid(n, block)), dim3(block), 0, stream, in,
+                       (__hip_bfloat16*)out, (int64_t)0, n, scale);
+    return;
+  }
   int64_t n16 = n / 16;
   if (n16 > 0) {
     hipLaunchKernelGGL(u8_to_bf16_scale_kernel,

@@ -35,14 +35,20 @@ __global__ void categorical_projection_kernel(
         float tz = r + gamma * ndr * z;
         tz = fminf(fmaxf(tz, v_min), v_max);
         float pos = (tz - v_min) / delta_z;
-        int64_t lo = (int64_t)floorf(pos);
-        int64_t hi = (int64_t)ceilf(pos);
+        float lo_f = floorf(pos);
+        float hi_f = ceilf(pos);
+        // fp32 (v_max - v_min) / delta_z can round to just above A-1
+        // (e.g. (-10, 10, A=124)), so ceil(pos) == A: the weights come
+        // from the unclamped position, the bins are clamped to the
+        // support (as c51_loss does) and the row keeps its mass.
+        int64_t lo = min(max((int64_t)lo_f, (int64_t)0), A - 1);
+        int64_t hi = min(max((int64_t)hi_f, (int64_t)0), A - 1);
         float p = next_dist[row * A + a];
-        if (lo == hi) {
+        if (lo_f == hi_f) {
           atomicAdd(&acc[wave][lo], p);
         } else {
-          atomicAdd(&acc[wave][lo], p * ((float)hi - pos));
-          atomicAdd(&acc[wave][hi], p * (pos - (float)lo));
+          atomicAdd(&acc[wave][lo], p * (hi_f - pos));
+          atomicAdd(&acc[wave][hi], p * (pos - lo_f));
         }
       }
     }

@@ -61,7 +61,7 @@ __global__ void sumtree_sample_kernel(const float* __restrict__ tree,
                                       int64_t* __restrict__ out,
                                       int64_t n, int64_t cap, int depth,
                                       int64_t size) {
-  __shared__ float top[SUMTREE_LDS_NODES];
+  __shared__ alignas(8) float top[SUMTREE_LDS_NODES];
   // cooperative stage of the top of the tree (coalesced float reads)
   int64_t stage = min((int64_t)SUMTREE_LDS_NODES, 2 * cap);
   for (int64_t i = threadIdx.x; i < stage; i += blockDim.x) {
@@ -75,9 +75,18 @@ __global__ void sumtree_sample_kernel(const float* __restrict__ tree,
     int64_t node = 1;
     for (int d = 0; d < depth; ++d) {
       int64_t left = node << 1;
-      float lw = (left + 1 < stage) ? top[left] : tree[left];
-      // branchless step: go right iff w > left subtree weight
-      bool right = w > lw;
+      // the two children as one 8-byte pair (left is even)
+      float2 ch = (left + 1 < stage)
+                      ? *reinterpret_cast<const float2*>(&top[left])
+                      : *reinterpret_cast<const float2*>(&tree[left]);
+      float lw = ch.x;
+      // Decision rule (stated in machin_amd/ops/sumtree.py): go right
+      // iff the right subtree holds weight and either w > left
+      // subtree weight or the left subtree is empty; a tie w == lw
+      // stays left. A zero-weight subtree is never entered: an empty
+      // right side keeps w == total on the left, an empty left side
+      // sends w == 0 to the right.
+      bool right = (ch.y > 0.0f) && (w > lw || !(lw > 0.0f));
       w = right ? (w - lw) : w;
       node = left + (right ? 1 : 0);
     }

@@ -89,14 +89,27 @@ class DeviceSumTree:
 
     # -- queries -------------------------------------------------------
     def find_leaf_index(self, prefix_weights: t.Tensor) -> t.Tensor:
-        """Map prefix weights in [0, sum) to leaf indexes."""
+        """Map prefix weights in the closed range [0, sum] to leaf
+        indexes.
+
+        The walk, the same on the device and in the CPU path: at each
+        node with children ``(lw, rw)`` and running prefix ``w``, go
+        right iff ``rw > 0 and (w > lw or lw <= 0)`` and then subtract
+        ``lw``; a tie ``w == lw`` stays left. With fp32 prefix sums
+        ``c`` leaf ``i`` therefore answers ``c[i-1] < u <= c[i]``, and
+        a subtree of zero weight is never entered: as long as the tree
+        holds any weight, no query (``0`` and ``sum`` included) returns
+        a zero-weight or padding leaf.
+        """
         u = prefix_weights.to(device=self.device, dtype=t.float32).contiguous()
         if self._ext is None:
             u = u.clone()
             idx = t.ones_like(u, dtype=t.long)
             for _ in range(self.depth):
                 left = self.weights[2 * idx]
-                right = (u >= left) & (left < self.weights[idx])
+                right = (self.weights[2 * idx + 1] > 0) & (
+                    (u > left) | ~(left > 0)
+                )
                 u = u - left * right
                 idx = 2 * idx + right.long()
             return (idx - self.capacity).clamp_(0, self.size - 1)
