@@ -39,9 +39,9 @@ from . import _load_ext, _require_ext, dequant_u8  # noqa: F401
 
 
 def _stem_kernels_fuse_relu() -> bool:
-    # the activation is fused into the v3 kernels only; the retired
+    # the activation is fused into the v3 and v4 kernels only; the retired
     # v1/v2 kernels (MACHIN_CONV1_V=1|2) keep the unfused composition
-    return os.environ.get("MACHIN_CONV1_V", "3") not in ("1", "2")
+    return os.environ.get("MACHIN_CONV1_V", "4") not in ("1", "2")
 
 
 class _FusedConv1Fn(t.autograd.Function):

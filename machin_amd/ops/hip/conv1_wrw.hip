@@ -205,6 +205,12 @@ __global__ void conv1_wrw_v3_kernel(const __bf16*, const unsigned char*,
                                     float);
 __global__ void conv1_fwd_v3_kernel(const unsigned char*, const __bf16*,
                                     const float*, __bf16*, int64_t, float);
+bool conv1_fwd_v4_launch(const unsigned char*, const void*, const float*,
+                         void*, unsigned int*, bool, int64_t, float,
+                         hipStream_t);
+bool conv1_wrw_v4_launch(const void*, const unsigned int*,
+                         const unsigned char*, float*, float*, int64_t,
+                         int64_t, float, hipStream_t);
 
 void conv1_wrw_launch(const void* dy, const unsigned char* frames,
                       float* scratch, float* grad_w, float* grad_b,
@@ -217,8 +223,18 @@ void conv1_wrw_launch(const void* dy, const unsigned char* frames,
   int64_t target_wg = 2048;
   if (const char* e = getenv("MACHIN_CONV1_WG")) target_wg = atol(e);
   const char* ver = getenv("MACHIN_CONV1_V");
-  int v = ver ? atoi(ver) : 3;
-  int64_t chunk = v == 3 ? 64 : 32;
+  int v = ver ? atoi(ver) : 4;
+  if (v != 1 && v != 2 && v != 3 &&
+      conv1_wrw_v4_launch(dy, nullptr, frames, scratch, grad_b, K,
+                          target_wg, scale, stream)) {
+    hipLaunchKernelGGL(conv1_wrw_reorder_kernel,
+                       dim3((CONV1_COUT * CONV1_N + 255) / 256), dim3(256),
+                       0, stream, scratch, grad_w);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  int64_t chunk = (v == 1 || v == 2) ? 32 : 64;
+  if (target_wg < 1) target_wg = 1;
   int64_t k_per_wg = (K + target_wg - 1) / target_wg;
   k_per_wg = ((k_per_wg + chunk - 1) / chunk) * chunk;
   if (k_per_wg < chunk) k_per_wg = chunk;
@@ -388,7 +404,12 @@ void conv1_fwd_launch(const unsigned char* frames, const void* weight,
                       float scale, hipStream_t stream) {
   int64_t grid = (K + FWD_ROWS - 1) / FWD_ROWS;
   const char* ver = getenv("MACHIN_CONV1_V");
-  int v = ver ? atoi(ver) : 3;
+  int v = ver ? atoi(ver) : 4;
+  if (v != 1 && v != 2 && v != 3 &&
+      conv1_fwd_v4_launch(frames, weight, bias, out, nullptr, false, K,
+                          scale, stream)) {
+    return;
+  }
   if (v == 1) {
     hipLaunchKernelGGL(conv1_fwd_kernel, dim3((unsigned)grid), dim3(256),
                        0, stream, frames, (const __bf16*)weight, bias,
@@ -1311,11 +1332,604 @@ void conv1_fwd_v3_relu_kernel(const unsigned char* __restrict__ frames,
   conv1_fwd_v3_body<true>(frames, weight, bias, out, mask, K, scale);
 }
 
-// fused-activation entry points (v3 kernels only)
+// =====================================================================
+// v4 forward: frame-resident, persistent workgroups.
+//
+// v3 spends its time on work the result does not need: every 128-row
+// workgroup (128 000 per step at batch 40960) restages the 16 KB
+// weight image, every pixel is fetched and dequantised once per patch
+// row it belongs to (the 8x8/stride-4 patches overlap 2x2), and each
+// workgroup runs eight barrier pairs around 32 MFMAs per wave.
+//
+// Here a workgroup owns whole frames (grid-stride loop over the batch):
+// - the 16 weight fragments (8 patch rows x 2 n-tiles) are read ONCE
+//   per workgroup and live in registers (64 VGPRs);
+// - a frame arrives as 1764 coalesced 16-byte loads, each pixel is
+//   dequantised once and the frame is kept in LDS as a bf16 NHWC image
+//   (56 448 B, two workgroups per CU);
+// - the A fragment of output position (oh, ow), patch row pr, quarter
+//   q is ONE aligned ds_read_b128 straight from that image: k = q*8+j
+//   is pixel ow*4 + q*2 + j/4, channel j%4 of image row oh*4 + pr,
+//   eight contiguous bf16;
+// - the next frame's seven 16-byte loads per thread are issued before
+//   the current frame's MFMAs, so they complete under them;
+// - two barriers per FRAME: image written -> fragments read -> image
+//   may be overwritten.
+// Same MFMA instruction, operand roles, k-slot assignment, pr order
+// and epilogue as v3, so the output and the mask are bit-identical.
+// =====================================================================
+#define FWD4_FRAME_ELEMS (84 * 84 * CONV1_CIN)   // 28224 u8 per frame
+#define FWD4_CHUNKS (FWD4_FRAME_ELEMS / 16)      // 1764 16-byte loads
+#define FWD4_LOADS ((FWD4_CHUNKS + 255) / 256)   // 7 per thread
+#define FWD4_TILES (CONV1_POS / 16)              // 25 m-tiles per frame
+#define FWD4_ROW_ELEMS (84 * CONV1_CIN)          // one image row
+
+template <bool RELU>
+__device__ __forceinline__
+void conv1_fwd_v4_body(const unsigned char* __restrict__ frames,
+                       const __bf16* __restrict__ weight,  // [256][32]
+                       const float* __restrict__ bias,
+                       __bf16* __restrict__ out,
+                       unsigned int* __restrict__ mask, int64_t B,
+                       float scale) {
+  __shared__ __attribute__((aligned(16))) __bf16 s_f[FWD4_FRAME_ELEMS];
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / MA_WAVE);
+  const int lane = tid % MA_WAVE;
+  const int col0 = lane & 15;
+  const int k0 = (lane >> 4) * 8;
+
+  // B fragments: lane holds W[pr*32 + k0 + j][h*16 + col0], j = 0..7
+  bf16x8 wf[CONV1_KSZ][2];
+#pragma unroll
+  for (int pr = 0; pr < CONV1_KSZ; ++pr) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const __bf16* w = weight + (pr * 32 + k0 + j) * 32 + col0;
+      wf[pr][0][j] = w[0];
+      wf[pr][1][j] = w[16];
+    }
+  }
+  const float bias0 = bias != nullptr ? bias[col0] : 0.0f;
+  const float bias1 = bias != nullptr ? bias[16 + col0] : 0.0f;
+
+  uint4 raw[FWD4_LOADS];
+  auto load_frame = [&](int64_t f) {
+    const uint4* src = (const uint4*)(frames + f * FWD4_FRAME_ELEMS);
+#pragma unroll
+    for (int i = 0; i < FWD4_LOADS; ++i) {
+      int idx = tid + i * 256;
+      // only the last of the seven rounds runs past the frame
+      if (i < FWD4_LOADS - 1 || idx < FWD4_CHUNKS) raw[i] = src[idx];
+    }
+  };
+
+  int64_t f = blockIdx.x;
+  if (f < B) load_frame(f);
+  for (; f < B; f += gridDim.x) {
+    // dequantise the prefetched frame once, into the LDS image
+#pragma unroll
+    for (int i = 0; i < FWD4_LOADS; ++i) {
+      int idx = tid + i * 256;
+      if (i < FWD4_LOADS - 1 || idx < FWD4_CHUNKS) {
+        unsigned int words[4] = {raw[i].x, raw[i].y, raw[i].z, raw[i].w};
+        bf16x8 q0, q1;
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            q0[w * 4 + j] = u8_bf16((words[w] >> (8 * j)) & 0xFF, scale);
+            q1[w * 4 + j] =
+                u8_bf16((words[w + 2] >> (8 * j)) & 0xFF, scale);
+          }
+        }
+        *(bf16x8*)(s_f + idx * 16) = q0;
+        *(bf16x8*)(s_f + idx * 16 + 8) = q1;
+      }
+    }
+    __syncthreads();  // image of frame f complete
+    if (f + gridDim.x < B) load_frame(f + gridDim.x);
+
+    __bf16* out_f = out + f * (CONV1_POS * 32);
+    for (int t = wave; t < FWD4_TILES; t += 4) {
+      const int pos = t * 16 + col0;
+      const int oh = pos / CONV1_OHW, ow = pos - oh * CONV1_OHW;
+      const __bf16* a_ptr =
+          s_f + (oh * CONV1_STRIDE * 84 + ow * CONV1_STRIDE) * CONV1_CIN
+          + k0;
+      f32x4 acc0 = (f32x4)(0.0f), acc1 = (f32x4)(0.0f);
+#pragma unroll
+      for (int pr = 0; pr < CONV1_KSZ; ++pr) {
+        bf16x8 a_frag = *(const bf16x8*)(a_ptr + pr * FWD4_ROW_ELEMS);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a_frag, wf[pr][0], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a_frag, wf[pr][1], acc1, 0, 0, 0);
+      }
+      // epilogue as v3 (C/D map: col=lane&15, row=(lane>>4)*4+reg)
+      const int row_base = t * 16 + (lane >> 4) * 4;
+      unsigned int row_mask = 0u;  // lanes 0..15: word of row t*16+lane
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        __bf16 v0 = (__bf16)(acc0[reg] + bias0);
+        __bf16 v1 = (__bf16)(acc1[reg] + bias1);
+        if constexpr (RELU) {
+          // !(v <= 0) keeps NaN, as ATen's relu does
+          bool p0 = !((float)v0 <= 0.0f);
+          bool p1 = !((float)v1 <= 0.0f);
+          // the 16-bit field q of the two ballots is the word of row
+          // q*4 + reg of this tile; lane l < 16 keeps the word of row l
+          unsigned long long m0 = __ballot(p0);
+          unsigned long long m1 = __ballot(p1);
+          int q = (lane >> 2) & 3;
+          unsigned int w =
+              (unsigned int)((m0 >> (q * 16)) & 0xFFFFull)
+              | ((unsigned int)((m1 >> (q * 16)) & 0xFFFFull) << 16);
+          if ((lane & 3) == reg) row_mask = w;
+          v0 = p0 ? v0 : (__bf16)0.0f;
+          v1 = p1 ? v1 : (__bf16)0.0f;
+        }
+        out_f[(row_base + reg) * 32 + col0] = v0;
+        out_f[(row_base + reg) * 32 + 16 + col0] = v1;
+      }
+      if constexpr (RELU) {
+        if (lane < 16) mask[f * CONV1_POS + t * 16 + lane] = row_mask;
+      }
+    }
+    __syncthreads();  // all fragment reads of frame f done
+  }
+}
+
+__global__ __launch_bounds__(256)
+void conv1_fwd_v4_kernel(const unsigned char* __restrict__ frames,
+                         const __bf16* __restrict__ weight,
+                         const float* __restrict__ bias,
+                         __bf16* __restrict__ out, int64_t B,
+                         float scale) {
+  conv1_fwd_v4_body<false>(frames, weight, bias, out, nullptr, B, scale);
+}
+
+__global__ __launch_bounds__(256)
+void conv1_fwd_v4_relu_kernel(const unsigned char* __restrict__ frames,
+                              const __bf16* __restrict__ weight,
+                              const float* __restrict__ bias,
+                              __bf16* __restrict__ out,
+                              unsigned int* __restrict__ mask, int64_t B,
+                              float scale) {
+  conv1_fwd_v4_body<true>(frames, weight, bias, out, mask, B, scale);
+}
+
+// CU count of the current device, queried once per device
+static int conv1_cu_count() {
+  static int cached[64] = {0};
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) dev = 0;
+  if (cached[dev] == 0) {
+    int n = 0;
+    HIP_CHECK(hipDeviceGetAttribute(
+        &n, hipDeviceAttributeMultiprocessorCount, dev));
+    cached[dev] = n > 0 ? n : 1;
+  }
+  return cached[dev];
+}
+
+// Launches the frame-resident forward (mask == nullptr: plain kernel).
+// Returns false without launching when its preconditions do not hold
+// (whole frames, 16-byte aligned frame base); the caller then runs v3.
+bool conv1_fwd_v4_launch(const unsigned char* frames, const void* weight,
+                         const float* bias, void* out, unsigned int* mask,
+                         bool relu, int64_t K, float scale,
+                         hipStream_t stream) {
+  if (K <= 0 || K % CONV1_POS != 0) return false;
+  if ((uintptr_t)frames % 16 != 0) return false;
+  const int64_t B = K / CONV1_POS;
+  // 56 KB of LDS per workgroup: two resident workgroups per CU. The
+  // grid is twice that, so that a CU which finishes early picks up
+  // another workgroup (0.533 against 0.551 ms at batch 40960, spread
+  // 0.005 ms; one workgroup per frame costs 0.64 ms)
+  int64_t grid = (int64_t)conv1_cu_count() * 4;
+  if (const char* e = getenv("MACHIN_CONV1_FWD_WG")) grid = atol(e);
+  if (grid < 1) grid = 1;
+  if (grid > B) grid = B;
+  if (relu) {
+    hipLaunchKernelGGL(conv1_fwd_v4_relu_kernel, dim3((unsigned)grid),
+                       dim3(256), 0, stream, frames,
+                       (const __bf16*)weight, bias, (__bf16*)out, mask, B,
+                       scale);
+  } else {
+    hipLaunchKernelGGL(conv1_fwd_v4_kernel, dim3((unsigned)grid),
+                       dim3(256), 0, stream, frames,
+                       (const __bf16*)weight, bias, (__bf16*)out, B,
+                       scale);
+  }
+  HIP_CHECK(hipGetLastError());
+  return true;
+}
+
+// =====================================================================
+// v4 weight gradient: frame-resident, no per-chunk transposition of x.
+//
+// v3 is bound by VALU issue (about 100 VALU instructions per MFMA):
+// 64-bit divisions per 4-byte frame load, and every pixel fetched,
+// dequantised and register-transposed once per patch it belongs to.
+//
+// Here a workgroup owns whole frames. Within one image row R the
+// im2col element of output column ow, patch column kw, channel ci is
+// row[ow*16 + kw*4 + ci]: with e = w*4 + ci the byte index in the row,
+// n' = e & 15 and ow' = e >> 4, patch columns 0..3 of position ow are
+// (n', ow' = ow) and patch columns 4..7 are (n' , ow' = ow + 1). So the
+// row is stored ONCE, transposed at staging time, as T[R][n'][ow']
+// (u8, ow' padded 21 -> 24), and
+//   dW[co][pr][n']      = sum_{oh,ow'} dy [oh][ow'][co] * T[oh*4+pr][n'][ow']
+//   dW[co][pr][16 + n'] = sum_{oh,ow'} dys[oh][ow'][co] * T[oh*4+pr][n'][ow']
+// with dys[oh][ow'] = dy[oh][ow' - 1] (zero at ow' = 0) and dy zero
+// for ow' >= 20. One B fragment (8 consecutive ow' of one (R, n'): one
+// ds_read_b64, dequantised in registers) feeds four MFMAs: two m-tiles
+// times {dy, dys}. The k-slots of an MFMA are positions: quarter q of
+// k-step s is the pair (oh, ow' group of 8) number s*4 + q, 60 pairs =
+// 15 k-steps per frame; positions inside a frame are small counters,
+// there is no division by 400 anywhere.
+//
+// dy is kept transposed as Dt[co][oh][24] bf16 (masked as it is written,
+// pads zero). The dys fragment is the dy fragment shifted by one
+// element: four v_alignbit with the dword in front of it, which is the
+// zero pad of the previous row for ow' = 0.
+//
+// Frames and dy arrive with 16- and 8-byte loads issued for frame f+1
+// before the MFMAs of frame f; each thread transposes 4x4 byte blocks
+// (x) and 8x4 bf16 blocks (dy) in registers on the way into LDS.
+// LDS: T 84*408 + Dt (8 + 32*488)*2 = 65 520 B, two workgroups per CU.
+// Wave w owns patch rows 2w and 2w+1: 2 pr x 2 halves x 2 m-tiles =
+// 8 accumulator tiles. Split-K epilogue as v3.
+// =====================================================================
+#define WRW4_T_ROW 408       // bytes per image row of T: 16 n' x 24 + pad
+#define WRW4_T_N 24          // bytes per (R, n')
+#define WRW4_DT_CO 488       // elements per channel of Dt: 20 x 24 + 8
+#define WRW4_DT_LEAD 8       // zero elements in front of channel 0
+#define WRW4_KSTEPS 15       // 20 rows x 3 groups of 8 / 4 quarters
+#define WRW4_X_TASKS (84 * 6)       // (row, 4 chunks of 16 B)
+#define WRW4_DY_TASKS (20 * 3 * 8)  // (oh, ow' group, 4 channels)
+
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+
+__device__ __forceinline__ unsigned int byte_perm(unsigned int hi,
+                                                  unsigned int lo,
+                                                  unsigned int sel) {
+  // result byte i = byte sel[i] of {hi, lo} (lo = bytes 0..3)
+  return __builtin_amdgcn_perm(hi, lo, sel);
+}
+
+// 0xFFFFFFFF if bit `bit` of w is set, else 0
+__device__ __forceinline__ unsigned int bit_fill(unsigned int w, int bit) {
+  return (unsigned int)((int)(w << (31 - bit)) >> 31);
+}
+
+__device__ __forceinline__ bf16x8 u8x8_bf16(uint2 r, float scale) {
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[j] = u8_bf16((r.x >> (8 * j)) & 0xFF, scale);
+    v[4 + j] = u8_bf16((r.y >> (8 * j)) & 0xFF, scale);
+  }
+  return v;
+}
+
+template <bool MASKED>
+__device__ __forceinline__
+void conv1_wrw_v4_body(const __bf16* __restrict__ dy,
+                       const unsigned int* __restrict__ mask,
+                       const unsigned char* __restrict__ frames,
+                       float* __restrict__ out,
+                       float* __restrict__ b_out, int64_t B,
+                       int64_t frames_per_wg, float scale) {
+  __shared__ __attribute__((aligned(16)))
+      unsigned char s_t[84 * WRW4_T_ROW];
+  __shared__ __attribute__((aligned(16)))
+      __bf16 s_dy[WRW4_DT_LEAD + CONV1_COUT * WRW4_DT_CO];
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / MA_WAVE);
+  const int lane = tid % MA_WAVE;
+  const int n16 = lane & 15;   // m of the A fragment, n' of the B one
+  const int q = lane >> 4;
+
+  // zero the pads nobody writes again: the lead and the 8 elements
+  // behind every channel (the dword in front of row 0 lies there)
+  if (tid <= CONV1_COUT) {
+    u32x4 z = {0u, 0u, 0u, 0u};
+    int at = tid == 0 ? 0
+                      : WRW4_DT_LEAD + (tid - 1) * WRW4_DT_CO
+                            + CONV1_OHW * 24;
+    *(u32x4*)(s_dy + at) = z;
+  }
+
+  // ---- staging tasks of this thread (fixed for the whole kernel) ----
+  // x: task (R, h) loads chunks 4h..4h+3 of image row R (21 per row)
+  int x_src[2], x_dst[2];
+  bool x_on[2], x_tail[2];
+  // dy: task (oh, g, cg) loads channels cg*4..+3 of positions g*8..+7
+  int dy_src[2], dy_dst[2], dy_pos[2];
+  bool dy_on[2], dy_tail[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    int task = tid + r * 256;
+    int R = task / 6, h = task - R * 6;
+    x_on[r] = task < WRW4_X_TASKS;
+    x_tail[r] = h == 5;  // only chunk 20 exists
+    x_src[r] = R * FWD4_ROW_ELEMS + h * 64;
+    x_dst[r] = R * WRW4_T_ROW + h * 4;
+    int cg = task & 7, rest = task >> 3;
+    int oh = rest / 3, g = rest - oh * 3;
+    dy_on[r] = task < WRW4_DY_TASKS;
+    dy_tail[r] = g == 2;  // positions 20..23 do not exist
+    dy_pos[r] = oh * CONV1_OHW + g * 8;
+    dy_src[r] = dy_pos[r] * CONV1_COUT + cg * 4;
+    dy_dst[r] = WRW4_DT_LEAD + cg * 4 * WRW4_DT_CO + oh * 24 + g * 8;
+  }
+
+  uint4 xr[2][4];
+  uint2 dr[2][8];
+  uint4 mlo[2], mhi[2];
+  auto load_frame = [&](int64_t f) {
+    const unsigned char* xf = frames + f * FWD4_FRAME_ELEMS;
+    const __bf16* df = dy + f * (CONV1_POS * CONV1_COUT);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        xr[r][i] = make_uint4(0u, 0u, 0u, 0u);
+        if (x_on[r] && (i == 0 || !x_tail[r])) {
+          xr[r][i] = *(const uint4*)(xf + x_src[r] + i * 16);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        dr[r][i] = make_uint2(0u, 0u);
+        if (dy_on[r] && (i < 4 || !dy_tail[r])) {
+          dr[r][i] = *(const uint2*)(df + dy_src[r] + i * CONV1_COUT);
+        }
+      }
+      if constexpr (MASKED) {
+        // 16-byte aligned: 400*f + 20*oh + 8*g words
+        const unsigned int* mf = mask + f * CONV1_POS + dy_pos[r];
+        mlo[r] = make_uint4(0u, 0u, 0u, 0u);
+        mhi[r] = make_uint4(0u, 0u, 0u, 0u);
+        if (dy_on[r]) {
+          mlo[r] = *(const uint4*)mf;
+          if (!dy_tail[r]) mhi[r] = *(const uint4*)(mf + 4);
+        }
+      }
+    }
+  };
+  auto store_frame = [&]() {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      if (x_on[r]) {
+        unsigned int in[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          in[i][0] = xr[r][i].x; in[i][1] = xr[r][i].y;
+          in[i][2] = xr[r][i].z; in[i][3] = xr[r][i].w;
+        }
+#pragma unroll
+        for (int dw = 0; dw < 4; ++dw) {
+          // 4x4 byte transpose: out j = byte j of chunks 0..3
+          unsigned int lo01 = byte_perm(in[1][dw], in[0][dw], 0x05010400u);
+          unsigned int hi01 = byte_perm(in[1][dw], in[0][dw], 0x07030602u);
+          unsigned int lo23 = byte_perm(in[3][dw], in[2][dw], 0x05010400u);
+          unsigned int hi23 = byte_perm(in[3][dw], in[2][dw], 0x07030602u);
+          unsigned int c[4] = {byte_perm(lo23, lo01, 0x05040100u),
+                               byte_perm(lo23, lo01, 0x07060302u),
+                               byte_perm(hi23, hi01, 0x05040100u),
+                               byte_perm(hi23, hi01, 0x07060302u)};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            *(unsigned int*)(s_t + x_dst[r] + (dw * 4 + j) * WRW4_T_N) =
+                c[j];
+          }
+        }
+      }
+      if (dy_on[r]) {
+        unsigned int dx[8], dyv[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          dx[i] = dr[r][i].x;
+          dyv[i] = dr[r][i].y;
+        }
+        if constexpr (MASKED) {
+          unsigned int mw[8] = {mlo[r].x, mlo[r].y, mlo[r].z, mlo[r].w,
+                                mhi[r].x, mhi[r].y, mhi[r].z, mhi[r].w};
+          const int c0 = ((tid + r * 256) & 7) * 4;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            unsigned int bits = mw[i] >> c0;
+            dx[i] &= (bit_fill(bits, 0) & 0x0000FFFFu)
+                     | (bit_fill(bits, 1) & 0xFFFF0000u);
+            dyv[i] &= (bit_fill(bits, 2) & 0x0000FFFFu)
+                      | (bit_fill(bits, 3) & 0xFFFF0000u);
+          }
+        }
+        // channel j of 8 positions: dword d = positions 2d, 2d+1
+        u32x4 o[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          o[0][d] = byte_perm(dx[2 * d + 1], dx[2 * d], 0x05040100u);
+          o[1][d] = byte_perm(dx[2 * d + 1], dx[2 * d], 0x07060302u);
+          o[2][d] = byte_perm(dyv[2 * d + 1], dyv[2 * d], 0x05040100u);
+          o[3][d] = byte_perm(dyv[2 * d + 1], dyv[2 * d], 0x07060302u);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          *(u32x4*)(s_dy + dy_dst[r] + j * WRW4_DT_CO) = o[j];
+        }
+      }
+    }
+  };
+
+  f32x4 acc[2][2][2];  // [pr of this wave][half][m-tile]
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      acc[a][b][0] = (f32x4)(0.0f);
+      acc[a][b][1] = (f32x4)(0.0f);
+    }
+  }
+  float bias_acc[2] = {0.0f, 0.0f};
+
+  const int64_t f_begin = (int64_t)blockIdx.x * frames_per_wg;
+  const int64_t f_end = min(f_begin + frames_per_wg, B);
+
+  if (f_begin < f_end) load_frame(f_begin);
+  for (int64_t f = f_begin; f < f_end; ++f) {
+    store_frame();
+    __syncthreads();  // images of frame f complete
+    if (f + 1 < f_end) load_frame(f + 1);
+
+#pragma unroll 3
+    for (int s = 0; s < WRW4_KSTEPS; ++s) {
+      const int p = s * 4 + q;
+      const int oh = p / 3, g = p - oh * 3;
+      const __bf16* ap =
+          s_dy + WRW4_DT_LEAD + n16 * WRW4_DT_CO + oh * 24 + g * 8;
+      const unsigned char* bp =
+          s_t + (oh * CONV1_STRIDE + wave * 2) * WRW4_T_ROW
+          + n16 * WRW4_T_N + g * 8;
+      u32x4 a[2];
+      unsigned int prev[2];
+      uint2 braw[2];
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) {
+        a[mt] = *(const u32x4*)(ap + mt * 16 * WRW4_DT_CO);
+        prev[mt] = *(const unsigned int*)(ap + mt * 16 * WRW4_DT_CO - 2);
+      }
+      braw[0] = *(const uint2*)bp;
+      braw[1] = *(const uint2*)(bp + WRW4_T_ROW);
+      bf16x8 af[2], as[2], bf[2];
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) {
+        u32x4 sh;
+        sh[0] = __builtin_amdgcn_alignbit(a[mt][0], prev[mt], 16);
+        sh[1] = __builtin_amdgcn_alignbit(a[mt][1], a[mt][0], 16);
+        sh[2] = __builtin_amdgcn_alignbit(a[mt][2], a[mt][1], 16);
+        sh[3] = __builtin_amdgcn_alignbit(a[mt][3], a[mt][2], 16);
+        af[mt] = __builtin_bit_cast(bf16x8, a[mt]);
+        as[mt] = __builtin_bit_cast(bf16x8, sh);
+      }
+      bf[0] = u8x8_bf16(braw[0], scale);
+      bf[1] = u8x8_bf16(braw[1], scale);
+      // fused bias: the waves take turns at summing the dy fragments
+      if ((s & 3) == wave) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) bias_acc[mt] += (float)af[mt][j];
+        }
+      }
+#pragma unroll
+      for (int prl = 0; prl < 2; ++prl) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          acc[prl][0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              af[mt], bf[prl], acc[prl][0][mt], 0, 0, 0);
+          acc[prl][1][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              as[mt], bf[prl], acc[prl][1][mt], 0, 0, 0);
+        }
+      }
+    }
+    __syncthreads();  // all fragment reads of frame f done
+  }
+
+  // ---- epilogue: split-K atomics (C/D map: col=lane&15,
+  // row=(lane>>4)*4+reg) ----------------------------------------------
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) {
+    float b = bias_acc[mt];
+    b += __shfl_down(b, 32, 64);
+    b += __shfl_down(b, 16, 64);
+    if (lane < 16) atomicAdd(&b_out[mt * 16 + lane], b);
+  }
+#pragma unroll
+  for (int prl = 0; prl < 2; ++prl) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) {
+        int col = (wave * 2 + prl) * 32 + half * 16 + n16;
+        int row_base = mt * 16 + q * 4;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          atomicAdd(&out[(row_base + reg) * CONV1_N + col],
+                    acc[prl][half][mt][reg]);
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256)
+void conv1_wrw_v4_kernel(const __bf16* __restrict__ dy,
+                         const unsigned char* __restrict__ frames,
+                         float* __restrict__ out,
+                         float* __restrict__ b_out, int64_t B,
+                         int64_t frames_per_wg, float scale) {
+  conv1_wrw_v4_body<false>(dy, nullptr, frames, out, b_out, B,
+                           frames_per_wg, scale);
+}
+
+__global__ __launch_bounds__(256)
+void conv1_wrw_v4_masked_kernel(const __bf16* __restrict__ dy,
+                                const unsigned int* __restrict__ mask,
+                                const unsigned char* __restrict__ frames,
+                                float* __restrict__ out,
+                                float* __restrict__ b_out, int64_t B,
+                                int64_t frames_per_wg, float scale) {
+  conv1_wrw_v4_body<true>(dy, mask, frames, out, b_out, B, frames_per_wg,
+                          scale);
+}
+
+// Launches the frame-resident weight-gradient kernel into the zeroed
+// scratch (mask == nullptr: unmasked). Returns false without launching
+// when its preconditions do not hold; the caller then runs v3.
+bool conv1_wrw_v4_launch(const void* dy, const unsigned int* mask,
+                         const unsigned char* frames, float* scratch,
+                         float* grad_b, int64_t K, int64_t target_wg,
+                         float scale, hipStream_t stream) {
+  if (K <= 0 || K % CONV1_POS != 0) return false;
+  if ((uintptr_t)frames % 16 != 0 || (uintptr_t)dy % 8 != 0 ||
+      (uintptr_t)mask % 16 != 0) {
+    return false;
+  }
+  const int64_t B = K / CONV1_POS;
+  if (target_wg < 1) target_wg = 1;
+  int64_t frames_per_wg = (B + target_wg - 1) / target_wg;
+  int grid = (int)((B + frames_per_wg - 1) / frames_per_wg);
+  if (mask != nullptr) {
+    hipLaunchKernelGGL(conv1_wrw_v4_masked_kernel, dim3(grid), dim3(256),
+                       0, stream, (const __bf16*)dy, mask, frames, scratch,
+                       grad_b, B, frames_per_wg, scale);
+  } else {
+    hipLaunchKernelGGL(conv1_wrw_v4_kernel, dim3(grid), dim3(256), 0,
+                       stream, (const __bf16*)dy, frames, scratch, grad_b,
+                       B, frames_per_wg, scale);
+  }
+  HIP_CHECK(hipGetLastError());
+  return true;
+}
+
+// fused-activation entry points (v3 and v4 kernels only)
 void conv1_fwd_relu_launch(const unsigned char* frames, const void* weight,
                            const float* bias, void* out,
                            unsigned int* mask, int64_t K, float scale,
                            hipStream_t stream) {
+  const char* ver = getenv("MACHIN_CONV1_V");
+  int v = ver ? atoi(ver) : 4;
+  if (v != 3 && conv1_fwd_v4_launch(frames, weight, bias, out, mask, true,
+                                    K, scale, stream)) {
+    return;
+  }
   int64_t grid = (K + FWD3_ROWS - 1) / FWD3_ROWS;
   hipLaunchKernelGGL(conv1_fwd_v3_relu_kernel, dim3((unsigned)grid),
                      dim3(256), 0, stream, frames, (const __bf16*)weight,
@@ -1333,6 +1947,16 @@ void conv1_wrw_masked_launch(const void* dy, const unsigned int* mask,
                            stream));
   int64_t target_wg = 2048;
   if (const char* e = getenv("MACHIN_CONV1_WG")) target_wg = atol(e);
+  const char* ver = getenv("MACHIN_CONV1_V");
+  int v = ver ? atoi(ver) : 4;
+  if (v != 3 && conv1_wrw_v4_launch(dy, mask, frames, scratch, grad_b, K,
+                                    target_wg, scale, stream)) {
+    hipLaunchKernelGGL(conv1_wrw_reorder_kernel,
+                       dim3((CONV1_COUT * CONV1_N + 255) / 256), dim3(256),
+                       0, stream, scratch, grad_w);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   if (target_wg < 1) target_wg = 1;
   int64_t k_per_wg = (K + target_wg - 1) / target_wg;
   k_per_wg = ((k_per_wg + KC3 - 1) / KC3) * KC3;

@@ -1,6 +1,7 @@
 """Microbenchmarks of the gfx950 kernels vs the reference CPU numbers.
 
 Run on a GPU box:  python tools/bench_kernels.py
+(`--conv1-only` runs just the stem conv A/B).
 Writes JSON to gpurun_out/kernel_bench.json.
 
 Reference CPU baselines:
@@ -30,7 +31,65 @@ def timeit(fn, iters=20, warmup=5):
     return (time.perf_counter() - t0) / iters * 1000.0  # ms
 
 
+def bench_conv1(results, ext, dev):
+    """Stem kernels, v1 / v3 / v4 A/B, at 1/5 of the bench's K and at the
+    bench's own K (batch 40960). The `relu` / `masked` entry points are
+    the ones the model runs; version 1 has no fused-activation form.
+    Version 4 is frame-resident in the forward; its weight gradient is
+    the v3 kernel."""
+    for Bc, tag in ((8192, "K3.3M"), (40960, "K16.4M")):
+        Kc = Bc * 400
+        frames_c = t.randint(0, 256, (Bc, 84, 84, 4), dtype=t.uint8,
+                             device=dev)
+        gy = (t.randn(Kc, 32, device=dev) * 0.1).to(t.bfloat16).contiguous()
+        wgt = (t.randn(256, 32, device=dev) * 0.1).to(
+            t.bfloat16
+        ).contiguous()
+        bias_c = t.zeros(32, device=dev)
+        mask_c = t.randint(-2 ** 31, 2 ** 31, (Kc,), device=dev,
+                           dtype=t.int64).to(t.int32)
+        for v in ("1", "3", "4"):
+            os.environ["MACHIN_CONV1_V"] = v
+            results[f"conv1_fwd_v{v}_{tag}_ms"] = timeit(
+                lambda: ext.conv1_fwd(frames_c, wgt, bias_c, 1.0 / 255.0),
+                iters=30,
+            )
+            results[f"conv1_wrw_v{v}_{tag}_ms"] = timeit(
+                lambda: ext.conv1_wrw(gy, frames_c, 1.0 / 255.0), iters=30
+            )
+            if v == "1":
+                continue
+            results[f"conv1_fwd_relu_v{v}_{tag}_ms"] = timeit(
+                lambda: ext.conv1_fwd_relu(frames_c, wgt, bias_c,
+                                           1.0 / 255.0),
+                iters=30,
+            )
+            results[f"conv1_wrw_masked_v{v}_{tag}_ms"] = timeit(
+                lambda: ext.conv1_wrw_masked(gy, mask_c, frames_c,
+                                             1.0 / 255.0),
+                iters=30,
+            )
+        os.environ.pop("MACHIN_CONV1_V", None)
+        del frames_c, gy, mask_c
+
+
+def write_results(results):
+    os.makedirs("gpurun_out", exist_ok=True)
+    with open("gpurun_out/kernel_bench.json", "w") as f:
+        json.dump(results, f, indent=2)
+    for k, v in results.items():
+        print(f"{k:40s} {v:10.3f}")
+
+
 def main():
+    if "--conv1-only" in sys.argv[1:]:
+        from machin_amd.ops import _machin_hip as ext
+
+        results = {}
+        bench_conv1(results, ext, t.device("cuda:0"))
+        write_results(results)
+        return
+
     from machin_amd.ops.sumtree import DeviceSumTree
     import machin_amd.ops as ops
     from machin_amd.frame.buffers import WeightTree
@@ -149,30 +208,8 @@ def main():
 
     results["nstep_64x4096_n3_torch_ms"] = timeit(nstep_torch)
 
-    # --- conv1 stem kernels: v1 vs v3 A/B at 1/5 bench K ------------
-    Bc = 8192
-    Kc = Bc * 400
-    frames_c = t.randint(0, 256, (Bc, 84, 84, 4), dtype=t.uint8,
-                         device=dev)
-    gy = (t.randn(Kc, 32, device=dev) * 0.1).to(t.bfloat16).contiguous()
-    wgt = (t.randn(256, 32, device=dev) * 0.1).to(t.bfloat16).contiguous()
-    bias_c = t.zeros(32, device=dev)
-    for v in ("1", "3"):
-        os.environ["MACHIN_CONV1_V"] = v
-        results[f"conv1_fwd_v{v}_K3.3M_ms"] = timeit(
-            lambda: ext.conv1_fwd(frames_c, wgt, bias_c, 1.0 / 255.0),
-            iters=30,
-        )
-        results[f"conv1_wrw_v{v}_K3.3M_ms"] = timeit(
-            lambda: ext.conv1_wrw(gy, frames_c, 1.0 / 255.0), iters=30
-        )
-    os.environ.pop("MACHIN_CONV1_V", None)
-
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/kernel_bench.json", "w") as f:
-        json.dump(results, f, indent=2)
-    for k, v in results.items():
-        print(f"{k:40s} {v:10.3f}")
+    bench_conv1(results, ext, dev)
+    write_results(results)
 
 
 if __name__ == "__main__":

@@ -48,7 +48,8 @@ def main():
     t1 = max(int(r[ekey]) for r in rows)
     t0 = cut
     frac = n_steps
-    agg = collections.defaultdict(lambda: [0, 0.0])
+    # calls, total ms, min ms, max ms of one dispatch
+    agg = collections.defaultdict(lambda: [0, 0.0, float("inf"), 0.0])
     total = 0.0
     for r in rows:
         if int(r[skey]) < cut:
@@ -64,19 +65,23 @@ def main():
             name = f"{name} [grid {grid}]"
         agg[name][0] += 1
         agg[name][1] += dur
+        agg[name][2] = min(agg[name][2], dur)
+        agg[name][3] = max(agg[name][3], dur)
         total += dur
     lines = [
         f"# Steady-state kernel profile: window = last {n_steps} "
         f"dispatches of '{anchor}' ({(t1 - t0) / 1e6:.0f} ms; MIOpen "
         f"autotune/find phases outside the window are EXCLUDED)",
         "",
-        "| % | total ms | calls | avg ms | kernel |",
-        "|---|---|---|---|---|",
+        "| % | total ms | calls | avg ms | min ms | max ms | kernel |",
+        "|---|---|---|---|---|---|---|",
     ]
-    for name, (calls, ms) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:top]:
+    for name, (calls, ms, lo, hi) in sorted(
+        agg.items(), key=lambda kv: -kv[1][1]
+    )[:top]:
         lines.append(
             f"| {ms / total * 100:5.1f} | {ms:9.2f} | {calls:5d} | "
-            f"{ms / calls:7.3f} | `{name}` |"
+            f"{ms / calls:7.3f} | {lo:7.3f} | {hi:7.3f} | `{name}` |"
         )
     text = "\n".join(lines) + "\n"
     print(text)
