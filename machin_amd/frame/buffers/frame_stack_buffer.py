@@ -46,7 +46,9 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
     Speaks the algorithm-facing API of :class:`DeviceTransitionBuffer`
     (``store_episode`` / ``store_transition`` / ``sample_batch`` /
     ``update_priority`` / ``size`` / ``clear``), so any algorithm takes
-    it through its ``replay_buffer=`` argument.
+    it through its ``replay_buffer=`` argument. :meth:`store_frames` is
+    the tensor path of ``store_episode`` for producers that already hold
+    an episode as a plane run (``DevicePixelCatchVecEnv(record=True)``).
 
     ``buffer_size`` is the capacity in FRAMES (ring planes), not in
     transitions: an episode of ``L`` transitions costs ``L + k`` slots,
@@ -211,20 +213,73 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
                 )
         if nexts.shape != states.shape:
             raise ValueError("state and next_state frame shapes differ.")
-        L = states.shape[0]
-        n = L + k
+        self._check_fits(states.shape[0])
+        if self.validate:
+            self._check_frames(states, nexts)
+        self._store_run(t.cat([states[0], nexts[:, -1]], dim=0), cols)
+
+    def store_frames(self, frames: t.Tensor, columns: Dict[str, t.Tensor]):
+        """The tensor path of :meth:`store_episode`: store one episode
+        of ``L`` transitions given as the plane run the frame ring
+        keeps.
+
+        ``frames`` is u8 ``[L + k, H, W]``, on any device: the ``k``
+        planes of the first state, then the newest plane of every
+        next_state (transition ``i`` has state ``frames[i : i + k]`` and
+        next_state ``frames[i + 1 : i + k + 1]``). ``columns`` maps the
+        names :meth:`flatten_episode` produces — ``"action/action"``,
+        ``"reward"``, ``"terminal"``, custom attributes, other
+        ``"state/..."`` keys — to ``[L, ...]`` tensors, on any device.
+
+        Eviction, priorities, counters and what sampling returns are
+        those of ``store_episode`` with the same episode. There is no
+        list of dicts, no sliding-window check (a plane run cannot
+        violate it); an episode whose tensors are all on a GPU is stored
+        with device copies only, without a host copy and without waiting
+        for the device (host tensors go through the pinned slabs as in
+        ``store_episode``)."""
+        k = self.frame_stack
+        if not t.is_tensor(frames) or frames.dtype != t.uint8 \
+                or frames.dim() != 3 or frames.shape[0] <= k:
+            raise ValueError(
+                f"frames must be a uint8 [L + {k}, H, W] tensor with "
+                f"L >= 1."
+            )
+        L = frames.shape[0] - k
+        cols = {}
+        for name, v in columns.items():
+            if name in (self._state_col, self._next_col, "_base", "_left"):
+                raise ValueError(f"Column {name!r} is made by the buffer.")
+            if not t.is_tensor(v) or v.dim() < 1 or v.shape[0] != L:
+                raise ValueError(
+                    f"Column {name!r} must be a tensor with {L} rows."
+                )
+            cols[name] = v.detach()
+        self._check_fits(L)
+        self._store_run(frames.detach(), cols)
+
+    def _check_fits(self, L: int):
+        n = L + self.frame_stack
         if n > self.buffer_size:
             raise ValueError(
                 f"Episode of {L} transitions needs {n} frame slots, "
                 f"buffer_size is {self.buffer_size}."
             )
-        if self.validate:
-            self._check_frames(states, nexts)
-        frames = t.cat([states[0], nexts[:, -1]], dim=0)
+
+    def _store_run(self, frames: t.Tensor, cols: Dict[str, t.Tensor]):
+        """Write one episode: its plane run ``[L + k, H, W]`` and its
+        other columns ``[L, ...]`` (shared by :meth:`store_episode` and
+        :meth:`store_frames`)."""
+        L = frames.shape[0] - self.frame_stack
+        n = frames.shape[0]
         with self._lock:
             F, T = self.buffer_size, self._t_capacity
             first = self._plane_count
-            cols["_base"] = t.arange(first, first + L, dtype=t.int64) % F
+            # index columns are born where the frames are: frames that
+            # already live on a GPU bring no host tensor along
+            idx_dev = frames.device if frames.is_cuda else None
+            cols["_base"] = t.arange(first, first + L, dtype=t.int64,
+                                     device=idx_dev) % F
             if self.n_step > 1:
                 for name in ("reward", "terminal"):
                     v = cols.get(name)
@@ -234,7 +289,8 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
                             f"float32 column."
                         )
                 # transitions that follow in the episode
-                cols["_left"] = t.arange(L - 1, -1, -1, dtype=t.int64)
+                cols["_left"] = t.arange(L - 1, -1, -1, dtype=t.int64,
+                                         device=idx_dev)
             self._ensure_rings(cols, tuple(frames.shape[1:]))
             # refuse before any bookkeeping changes
             if frames.shape[1:] != self._planes.shape[1:]:
@@ -257,8 +313,13 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
                 if ep[1] == 0:
                     self._episodes.popleft()
             self._live -= killed
-            # -- one H2D copy per column through the pinned slabs
-            staged = self._stage({**cols, "_frames": frames})
+            # -- one H2D copy per host column through the pinned slabs
+            # (an episode that is on a GPU already skips the slabs and
+            # the wait for their previous copies)
+            staged = {**cols, "_frames": frames}
+            from_host = any(not v.is_cuda for v in staged.values())
+            if from_host:
+                staged = self._stage(staged)
             frames = staged.pop("_frames").to(
                 self.buffer_device, non_blocking=True
             )
@@ -269,7 +330,7 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
                 self._planes[h:] = frames[: F - h]
                 self._planes[: h + n - F] = frames[F - h :]
             pos = self._inner.store_batch(staged)
-            if self._pinned_event is not None:
+            if from_host and self._pinned_event is not None:
                 self._pinned_event.record()
             if self._tree is not None:
                 # killed slots that the new transitions do not reuse

@@ -904,11 +904,345 @@ def framestack_gather_nstep(
     )
 
 
+# ======================================================================
+# batched device PixelCatch (machin_amd/ops/hip/pixelcatch.hip)
+# ======================================================================
+_PC_H = _PC_W = 84
+_PC_STATE = 10  # paddle_x ball_x ball_y balls_left steps done hist0..3
+_M32 = 0xFFFFFFFF
+
+
+def _mulhilo32(m: int, x: t.Tensor):
+    """(lo, hi) words of ``m * x`` for a 32-bit constant ``m`` and
+    int64 tensors holding 32-bit values, without leaving int64."""
+    a = m * (x & 0xFFFF)  # < 2^48
+    s = m * (x >> 16) + (a >> 16)  # < 2^49
+    return ((s & 0xFFFF) << 16) | (a & 0xFFFF), s >> 16
+
+
+def _philox4x32_10_first(seed: int, offset: t.Tensor, subseq: t.Tensor):
+    """Word 0 of Philox4x32-10 with key ``seed`` and counter ``(offset
+    lo, offset hi, subseq lo, subseq hi)`` — ``ma_philox4`` of common.h
+    as int64 tensor arithmetic."""
+    k0, k1 = seed & _M32, (seed >> 32) & _M32
+    c0, c1 = offset & _M32, (offset >> 32) & _M32
+    c2, c3 = subseq & _M32, (subseq >> 32) & _M32
+    for _ in range(10):
+        lo0, hi0 = _mulhilo32(0xD2511F53, c0)
+        lo1, hi1 = _mulhilo32(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0
+
+
+def _pixelcatch_spawn_x(seed: int, ball_no: t.Tensor) -> t.Tensor:
+    env = t.arange(ball_no.shape[0], device=ball_no.device)
+    return 3 + _philox4x32_10_first(int(seed), ball_no, env) % 78
+
+
+def _pixelcatch_pack(px, bx, by):
+    return px | (bx << 8) | (by << 16) | (1 << 24)
+
+
+def _pixelcatch_render(hist: t.Tensor) -> t.Tensor:
+    """Packed history entries ``[...]`` -> u8 planes ``[..., 84, 84]``
+    (``PixelCatchEnv._frame``; an invalid entry is a zero plane)."""
+    h = hist.long()[..., None, None]
+    px, bx, by = h & 255, (h >> 8) & 255, (h >> 16) & 255
+    valid = ((h >> 24) & 1).bool()
+    r = t.arange(_PC_H, device=hist.device).view(_PC_H, 1)
+    c = t.arange(_PC_W, device=hist.device).view(1, _PC_W)
+    paddle = (r >= _PC_H - 3) & (c >= px - 4) & (c < px + 4)
+    ball = (r >= by - 1) & (r <= by + 1) & (c >= bx - 1) & (c <= bx + 1)
+    return (valid & (paddle | ball)).to(t.uint8) * 255
+
+
+def _pixelcatch_check(state, ball_no, obs, others):
+    """Shared argument validation of the PixelCatch ops. ``others`` is
+    a list of ``(name, tensor, dtype, numel)``."""
+    if state.dim() != 2 or state.shape[1] != _PC_STATE \
+            or state.dtype != t.int32 or not state.is_contiguous():
+        raise ValueError("state must be a contiguous int32 [E, 10] tensor")
+    E = state.shape[0]
+    if obs.dtype != t.uint8 or tuple(obs.shape) != (E, 4, _PC_H, _PC_W):
+        raise ValueError("obs must be uint8 [E, 4, 84, 84]")
+    plane = _PC_H * _PC_W
+    if obs.stride() not in ((4 * plane, plane, _PC_W, 1),
+                            (4 * plane, 1, 4 * _PC_W, 4)):
+        raise ValueError(
+            "obs must be contiguous or in channels_last strides"
+        )
+    for name, x, dtype, numel in [("ball_no", ball_no, t.int64, E)] + others:
+        if x.dtype != dtype or x.numel() != numel or not x.is_contiguous():
+            raise ValueError(
+                f"{name} must be a contiguous {dtype} tensor of {numel} "
+                f"elements"
+            )
+    for name, x in [("ball_no", ball_no), ("obs", obs)] + [
+        (name, x) for name, x, _, _ in others
+    ]:
+        if x.device != state.device:
+            raise ValueError(f"{name} must be on state's device")
+
+
+def _pixelcatch_step_check(state, ball_no, action, obs, frame, reward, done,
+                           ep_len, balls, max_episode_steps, log):
+    E = state.shape[0] if state.dim() == 2 else 0
+    others = [
+        ("action", action, t.int64, E),
+        ("frame", frame, t.uint8, E * _PC_H * _PC_W),
+        ("reward", reward, t.float32, E),
+        ("done", done, t.float32, E),
+        ("ep_len", ep_len, t.int32, E),
+    ]
+    if log is not None:
+        if len(log) != 4:
+            raise ValueError(
+                "log is (log_frames, log_action, log_reward, log_terminal)"
+            )
+        frames = log[0]
+        if frames.dim() != 4 or frames.shape[0] != E \
+                or frames.shape[1] <= 4 \
+                or tuple(frames.shape[2:]) != (_PC_H, _PC_W):
+            raise ValueError(
+                "log_frames must be [E, max_len + 4, 84, 84]"
+            )
+        max_len = frames.shape[1] - 4
+        others += [
+            ("log_frames", frames, t.uint8, frames.numel()),
+            ("log_action", log[1], t.int64, E * max_len),
+            ("log_reward", log[2], t.float32, E * max_len),
+            ("log_terminal", log[3], t.float32, E * max_len),
+        ]
+    _pixelcatch_check(state, ball_no, obs, others)
+    if not 1 <= int(balls) <= 2 ** 20:
+        raise ValueError("balls must be in [1, 2^20]")
+    if not 1 <= int(max_episode_steps) <= 2 ** 30:
+        raise ValueError("max_episode_steps must be in [1, 2^30]")
+
+
+def _pixelcatch_step_torch(
+    state: t.Tensor, ball_no: t.Tensor, action: t.Tensor, obs: t.Tensor,
+    frame: t.Tensor, reward: t.Tensor, done: t.Tensor, ep_len: t.Tensor,
+    seed: int, balls: int, max_episode_steps: int, auto_reset: bool = True,
+    log=None,
+):
+    """Torch composition of :func:`pixelcatch_step` (the CPU path and
+    the reference the kernel is tested and timed against; it also runs
+    on device tensors, without waiting for the device)."""
+    dev = state.device
+    E = state.shape[0]
+    st = state.long()
+    px, bx, by, left, steps, latched = (st[:, i] for i in range(6))
+    hist = st[:, 6:]
+    no = ball_no.clone()
+    env = t.arange(E, device=dev)
+    if auto_reset:
+        live = t.ones(E, dtype=t.bool, device=dev)
+    else:
+        live = latched == 0
+    act = action.reshape(E).clamp(0, 2)
+
+    px = (px + (act - 1) * 3).clamp(4, _PC_W - 4)
+    by = by + 3
+    landed = by >= _PC_H - 3
+    caught = (bx - px).abs() <= 5
+    one = t.ones(E, dtype=t.float32, device=dev)
+    rew = t.where(landed, t.where(caught, one, -one), t.zeros_like(one))
+    left = left - landed.long()
+    dn = landed & (left <= 0)
+    spawn = landed & ~dn
+    bx = t.where(spawn, _pixelcatch_spawn_x(seed, no), bx)
+    by = t.where(spawn, t.zeros_like(by), by)
+    no = no + spawn.long()
+    length = steps + 1
+    dn = dn | (length >= int(max_episode_steps))
+    newest = _pixelcatch_pack(px, bx, by)
+    pushed = t.cat([hist[:, 1:], newest.view(E, 1)], dim=1)
+    new_frame = _pixelcatch_render(newest)
+    frame.copy_(t.where(live.view(E, 1, 1), new_frame, frame.view(
+        E, _PC_H, _PC_W)).view(frame.shape))
+
+    if log is not None:
+        log_frames, log_action, log_reward, log_terminal = log
+        max_len = log_frames.shape[1] - 4
+        ok = live & (steps >= 0) & (steps < max_len)
+        # masked scatter without reading a mask back: rows that do not
+        # log rewrite what is there
+        col = t.where(ok, steps, t.zeros_like(steps))
+        head = log_frames[:, :4]
+        head.copy_(t.where((ok & (steps == 0)).view(E, 1, 1, 1),
+                           _pixelcatch_render(hist), head))
+        log_frames[env, col + 4] = t.where(
+            ok.view(E, 1, 1), new_frame, log_frames[env, col + 4]
+        )
+        for dst, val in (
+            (log_action.view(E, max_len), act),
+            (log_reward.view(E, max_len), rew),
+            (log_terminal.view(E, max_len), dn.float()),
+        ):
+            dst[env, col] = t.where(ok, val, dst[env, col])
+
+    steps = length
+    latched = dn.long()
+    if auto_reset:
+        fresh = _pixelcatch_spawn_x(seed, no)
+        no = no + dn.long()
+        px = t.where(dn, t.full_like(px, _PC_W // 2), px)
+        bx = t.where(dn, fresh, bx)
+        by = t.where(dn, t.zeros_like(by), by)
+        left = t.where(dn, t.full_like(left, int(balls)), left)
+        steps = t.where(dn, t.zeros_like(steps), steps)
+        first = t.zeros_like(pushed)
+        first[:, 3] = _pixelcatch_pack(px, bx, by)
+        pushed = t.where(dn.view(E, 1), first, pushed)
+        latched = t.zeros_like(latched)
+    obs.copy_(t.where(live.view(E, 1, 1, 1), _pixelcatch_render(pushed), obs))
+    new_state = t.cat(
+        [t.stack([px, bx, by, left, steps, latched], dim=1), pushed], dim=1
+    )
+    state.copy_(t.where(live.view(E, 1), new_state, st))
+    ball_no.copy_(t.where(live, no, ball_no))
+    reward.copy_(t.where(live, rew, t.zeros_like(rew)).view(reward.shape))
+    done.copy_(t.where(live, dn.float(), one).view(done.shape))
+    ep_len.copy_(
+        t.where(live & dn, length, t.zeros_like(length)).view(ep_len.shape)
+    )
+
+
+def _pixelcatch_reset_torch(state: t.Tensor, ball_no: t.Tensor,
+                            mask: t.Tensor, obs: t.Tensor, seed: int,
+                            balls: int):
+    """Torch composition of :func:`pixelcatch_reset`."""
+    E = state.shape[0]
+    m = mask.reshape(E) != 0
+    st = state.long()
+    fresh = t.zeros_like(st)
+    fresh[:, 0] = _PC_W // 2
+    fresh[:, 1] = _pixelcatch_spawn_x(seed, ball_no)
+    fresh[:, 3] = int(balls)
+    fresh[:, 9] = _pixelcatch_pack(fresh[:, 0], fresh[:, 1], fresh[:, 2])
+    st = t.where(m.view(E, 1), fresh, st)
+    state.copy_(st)
+    ball_no.add_(m.long())
+    obs.copy_(t.where(m.view(E, 1, 1, 1), _pixelcatch_render(st[:, 6:]), obs))
+
+
+def pixelcatch_step(
+    state: t.Tensor, ball_no: t.Tensor, action: t.Tensor, obs: t.Tensor,
+    frame: t.Tensor, reward: t.Tensor, done: t.Tensor, ep_len: t.Tensor,
+    seed: int, balls: int, max_episode_steps: int, auto_reset: bool = True,
+    log=None,
+) -> None:
+    """Step and render ``E`` PixelCatch envs in place; one env step is
+    ``PixelCatchEnv.step`` followed by the optional reset.
+
+    Per-env state (written in place): ``state`` int32 ``[E, 10]`` with
+    columns ``paddle_x, ball_x, ball_y, balls_left, steps, done`` and a
+    4-entry frame history, newest last, each entry packed as
+    ``paddle_x | ball_x << 8 | ball_y << 16 | valid << 24``; ``ball_no``
+    int64 ``[E]``, the number of balls the env has ever spawned.
+    ``action`` is int64 ``[E]``. Outputs (overwritten): ``obs`` u8
+    ``[E, 4, 84, 84]``, plain contiguous or in ``channels_last``
+    strides, channel 3 the newest; ``frame`` u8 ``[E, 84, 84]``;
+    ``reward`` and ``done`` f32 ``[E]``; ``ep_len`` int32 ``[E]``.
+
+    For env ``e`` (constants of ``pixel_catch.py``)::
+
+        a = clamp(action[e], 0, 2)
+        paddle_x = clip(paddle_x + 3 (a - 1), 4, 80);  ball_y += 3
+        if ball_y >= 81:
+            reward = +1 if |ball_x - paddle_x| <= 5 else -1
+            balls_left -= 1
+            done if balls_left <= 0, else spawn a ball
+        steps += 1;  done if steps >= max_episode_steps
+        push (paddle_x, ball_x, ball_y) into the history
+        frame[e]  = the newest plane (the terminal frame included)
+        ep_len[e] = steps if done else 0
+        if done and auto_reset:
+            paddle_x = 42, balls_left = balls, steps = 0, spawn a ball,
+            history = three invalid (zero) planes + the first frame
+        obs[e] = the history, rendered
+
+    The host env raises on an action outside ``{0, 1, 2}``; a kernel
+    cannot raise without a sync, so the action is clamped. With
+    ``auto_reset=False`` a done env is latched: later steps leave its
+    state, ``obs``, ``frame`` and log alone and return reward 0, done 1
+    and ``ep_len`` 0 until :func:`pixelcatch_reset`.
+
+    Spawning a ball: ``ball_x = 3 + philox4x32_10(key=seed,
+    counter=(ball_no lo, ball_no hi, e lo, e hi))[0] % 78``, then
+    ``ball_no += 1`` and ``ball_y = 0``. The range is ``[3, 81)`` as in
+    the host env; the modulo bias is 78 / 2^32. The host env's Mersenne
+    stream is deliberately not reproduced.
+
+    Rendering is ``PixelCatchEnv._frame``: paddle rows 81..83, columns
+    ``[paddle_x - 4, paddle_x + 4)``; ball rows ``[ball_y - 1, ball_y +
+    1]`` and columns ``[ball_x - 1, ball_x + 1]``, clipped to the
+    screen, value 255, the ball drawn over the paddle.
+
+    ``log = (log_frames [E, max_len + 4, 84, 84] u8, log_action
+    [E, max_len] int64, log_reward [E, max_len] f32, log_terminal
+    [E, max_len] f32)`` records episodes: the step with in-episode index
+    ``s`` (``steps`` before the step, ``s < max_len``) writes ``frame``
+    to slot ``4 + s`` and the clamped action, reward and done to column
+    ``s``; the step with ``s == 0`` also writes the four planes of the
+    episode's first state to slots 0..3 (the reset itself does not, so
+    a finished episode's log stays intact until the env's next step).
+    Slots ``[0, L + 4)`` are then the ``frames`` of
+    ``DeviceFrameStackBuffer.store_frames``.
+
+    On ROCm this is one gfx950 kernel launch on the current stream
+    (machin_amd/ops/hip/pixelcatch.hip), a pure write stream of 16-byte
+    stores; the CPU fallback is the same semantics as a torch
+    composition.
+    """
+    log = None if log is None else tuple(log)
+    _pixelcatch_step_check(state, ball_no, action, obs, frame, reward, done,
+                           ep_len, balls, max_episode_steps, log)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if state.is_cuda:
+        ext = _require_ext()
+        ext.pixelcatch_step(
+            state, ball_no, action, obs, frame, reward, done, ep_len, seed,
+            int(balls), int(max_episode_steps), bool(auto_reset),
+            *(log if log is not None else (None,) * 4),
+        )
+        return
+    _pixelcatch_step_torch(
+        state, ball_no, action, obs, frame, reward, done, ep_len, seed,
+        int(balls), int(max_episode_steps), bool(auto_reset), log,
+    )
+
+
+def pixelcatch_reset(state: t.Tensor, ball_no: t.Tensor, mask: t.Tensor,
+                     obs: t.Tensor, seed: int, balls: int) -> None:
+    """Reset the envs of :func:`pixelcatch_step` whose ``mask`` (u8
+    ``[E]``) is non-zero, in place: ``paddle_x = 42``, ``balls_left =
+    balls``, ``steps = 0``, ``done = 0``, a new ball, history = three
+    invalid entries + the first frame, and ``obs[e]`` = three zero
+    planes + that frame (``PixelCatchEnv.reset()``). Other envs and
+    every log are left alone."""
+    E = state.shape[0] if state.dim() == 2 else 0
+    _pixelcatch_check(state, ball_no, obs, [("mask", mask, t.uint8, E)])
+    if not 1 <= int(balls) <= 2 ** 20:
+        raise ValueError("balls must be in [1, 2^20]")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if state.is_cuda:
+        _require_ext().pixelcatch_reset(
+            state, ball_no, mask, obs, seed, int(balls)
+        )
+        return
+    _pixelcatch_reset_torch(state, ball_no, mask, obs, seed, int(balls))
+
+
 __all__ = [
     "available",
     "dequant_u8",
     "framestack_gather",
     "framestack_gather_nstep",
+    "pixelcatch_step",
+    "pixelcatch_reset",
     "polyak_update_",
     "discounted_returns",
     "gae",

@@ -66,6 +66,14 @@ void framestack_gather_nstep_launch(
     const float*, const int64_t*, unsigned char*, unsigned char*, float*,
     float*, int64_t*, int64_t, int64_t, int64_t, int64_t, int, int, float,
     bool, hipStream_t);
+void pixelcatch_step_launch(int32_t*, int64_t*, const int64_t*,
+                            unsigned char*, unsigned char*, float*, float*,
+                            int32_t*, unsigned char*, int64_t*, float*,
+                            float*, int64_t, uint64_t, int, int, int, bool,
+                            bool, hipStream_t);
+void pixelcatch_reset_launch(int32_t*, int64_t*, const unsigned char*,
+                             unsigned char*, int64_t, uint64_t, int, bool,
+                             hipStream_t);
 void pg_head_fwd_launch(const void*, const int64_t*, float*, float*,
                         int64_t, int, hipStream_t);
 void pg_head_bwd_launch(const void*, const int64_t*, const float*,
@@ -641,6 +649,107 @@ std::vector<Tensor> framestack_gather_nstep(Tensor planes, Tensor base,
   return {state, next, reward_n, terminal_n, steps};
 }
 
+// batched device PixelCatch (pixelcatch.hip). Everything is written in
+// place; obs is [E, 4, 84, 84] u8, contiguous or in channels_last
+// strides. Returns whether obs was taken as NHWC.
+bool pixelcatch_check_env(const Tensor& state, const Tensor& ball_no,
+                          const Tensor& obs) {
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kInt &&
+                  state.is_contiguous() && state.dim() == 2 &&
+                  state.size(1) == 10,
+              "state must be contiguous int32 [E, 10] CUDA");
+  const int64_t E = state.size(0);
+  check_arg(ball_no, state, at::kLong, E, "ball_no");
+  TORCH_CHECK(obs.is_cuda() && obs.device() == state.device() &&
+                  obs.scalar_type() == at::kByte && obs.dim() == 4 &&
+                  obs.size(0) == E && obs.size(1) == 4 &&
+                  obs.size(2) == 84 && obs.size(3) == 84,
+              "obs must be uint8 [E, 4, 84, 84] on state's device");
+  const bool nhwc = obs.stride(1) == 1;
+  if (nhwc) {
+    TORCH_CHECK(obs.stride(0) == 28224 && obs.stride(2) == 336 &&
+                    obs.stride(3) == 4,
+                "obs must be contiguous or in channels_last strides");
+  } else {
+    TORCH_CHECK(obs.stride(0) == 28224 && obs.stride(1) == 7056 &&
+                    obs.stride(2) == 84 && obs.stride(3) == 1,
+                "obs must be contiguous or in channels_last strides");
+  }
+  TORCH_CHECK((uintptr_t)obs.data_ptr() % 16 == 0,
+              "obs must be 16-byte aligned");
+  return nhwc;
+}
+
+void pixelcatch_step(Tensor state, Tensor ball_no, Tensor action, Tensor obs,
+                     Tensor frame, Tensor reward, Tensor done, Tensor ep_len,
+                     uint64_t seed, int64_t balls, int64_t max_episode_steps,
+                     bool auto_reset, c10::optional<Tensor> log_frames,
+                     c10::optional<Tensor> log_action,
+                     c10::optional<Tensor> log_reward,
+                     c10::optional<Tensor> log_terminal) {
+  const bool nhwc = pixelcatch_check_env(state, ball_no, obs);
+  const int64_t E = state.size(0);
+  check_arg(action, state, at::kLong, E, "action");
+  check_arg(frame, state, at::kByte, E * 7056, "frame");
+  check_arg(reward, state, at::kFloat, E, "reward");
+  check_arg(done, state, at::kFloat, E, "done");
+  check_arg(ep_len, state, at::kInt, E, "ep_len");
+  TORCH_CHECK((uintptr_t)frame.data_ptr() % 16 == 0,
+              "frame must be 16-byte aligned");
+  TORCH_CHECK(balls >= 1 && balls <= (1 << 20), "balls must be in [1, 2^20]");
+  TORCH_CHECK(max_episode_steps >= 1 && max_episode_steps <= (1 << 30),
+              "max_episode_steps must be in [1, 2^30]");
+  unsigned char* lf = nullptr;
+  int64_t* la = nullptr;
+  float* lr = nullptr;
+  float* lt = nullptr;
+  int64_t max_len = 0;
+  if (log_frames.has_value()) {
+    TORCH_CHECK(log_action.has_value() && log_reward.has_value() &&
+                    log_terminal.has_value(),
+                "the four log tensors come together");
+    const Tensor& f = *log_frames;
+    TORCH_CHECK(f.dim() == 4 && f.size(0) == E && f.size(1) > 4 &&
+                    f.size(2) == 84 && f.size(3) == 84,
+                "log_frames must be [E, max_len + 4, 84, 84]");
+    max_len = f.size(1) - 4;
+    TORCH_CHECK(max_len <= (1 << 30), "log too long");
+    check_arg(f, state, at::kByte, E * (max_len + 4) * 7056, "log_frames");
+    check_arg(*log_action, state, at::kLong, E * max_len, "log_action");
+    check_arg(*log_reward, state, at::kFloat, E * max_len, "log_reward");
+    check_arg(*log_terminal, state, at::kFloat, E * max_len,
+              "log_terminal");
+    TORCH_CHECK((uintptr_t)f.data_ptr() % 16 == 0,
+                "log_frames must be 16-byte aligned");
+    lf = f.data_ptr<unsigned char>();
+    la = log_action->data_ptr<int64_t>();
+    lr = log_reward->data_ptr<float>();
+    lt = log_terminal->data_ptr<float>();
+  }
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(state.device());
+  pixelcatch_step_launch(
+      state.data_ptr<int32_t>(), ball_no.data_ptr<int64_t>(),
+      action.data_ptr<int64_t>(), obs.data_ptr<unsigned char>(),
+      frame.data_ptr<unsigned char>(), reward.data_ptr<float>(),
+      done.data_ptr<float>(), ep_len.data_ptr<int32_t>(), lf, la, lr, lt, E,
+      seed, (int)balls, (int)max_episode_steps, (int)max_len, auto_reset,
+      nhwc, current_stream());
+}
+
+void pixelcatch_reset(Tensor state, Tensor ball_no, Tensor mask, Tensor obs,
+                      uint64_t seed, int64_t balls) {
+  const bool nhwc = pixelcatch_check_env(state, ball_no, obs);
+  const int64_t E = state.size(0);
+  check_arg(mask, state, at::kByte, E, "mask");
+  TORCH_CHECK(balls >= 1 && balls <= (1 << 20), "balls must be in [1, 2^20]");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(state.device());
+  pixelcatch_reset_launch(state.data_ptr<int32_t>(),
+                          ball_no.data_ptr<int64_t>(),
+                          mask.data_ptr<unsigned char>(),
+                          obs.data_ptr<unsigned char>(), E, seed, (int)balls,
+                          nhwc, current_stream());
+}
+
 std::vector<Tensor> conv1_wrw(Tensor dy, Tensor frames, double scale) {
   // dy: [K, 32] bf16 (NHWC-flattened conv output grad);
   // frames: [B, 84, 84, 4] u8. Returns [32, 4, 8, 8] fp32 grad.
@@ -924,6 +1033,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("u8_to_bf16_scale", &u8_to_bf16_scale);
   m.def("framestack_gather", &framestack_gather);
   m.def("framestack_gather_nstep", &framestack_gather_nstep);
+  m.def("pixelcatch_step", &pixelcatch_step);
+  m.def("pixelcatch_reset", &pixelcatch_reset);
   m.def("pg_head_fwd", &pg_head_fwd);
   m.def("pg_head_bwd", &pg_head_bwd);
   m.def("conv1_wrw", &conv1_wrw);

@@ -29,6 +29,7 @@ SOURCES = [
     "distributions.hip",
     "elementwise.hip",
     "framestack.hip",
+    "pixelcatch.hip",
     "conv1_wrw.hip",
     "bias_act.hip",
 ]
