@@ -19,6 +19,14 @@ values. It is required by ``dist_from_logits`` and by
 ``discount ** m`` for the ``m`` steps its n-step window really covers
 (needs a replay buffer that returns ``m`` as the ``n_step`` attribute,
 i.e. ``DeviceFrameStackBuffer(n_step > 1)``).
+
+``noisy_nets=True`` explores with noisy networks instead of epsilon:
+both nets must contain :class:`machin_amd.model.nets.NoisyLinear`
+layers (e.g. a ``NoisyDuelingC51Head``). ``update`` draws new,
+independent noise for the online and the target net before the
+forwards, ``act_discrete_with_noise`` draws new noise for the online
+net and returns the argmax of every row (no epsilon, no host RNG read),
+and ``act_discrete`` runs with the noise switched off.
 """
 from typing import Any, Dict, List, Union
 
@@ -27,6 +35,7 @@ import torch as t
 import torch.nn as nn
 
 from ... import ops
+from ...model.nets.noisy import noise_enabled, noisy_layers, reset_noise
 from ..buffers.prioritized_buffer import PrioritizedBuffer
 from ..transition import Transition
 from .dqn_per import DQNPer
@@ -50,6 +59,7 @@ class RAINBOW(DQNPer):
         fused_loss: bool = False,
         dist_from_logits: bool = False,
         exact_nstep_bootstrap: bool = False,
+        noisy_nets: bool = False,
         **kwargs,
     ):
         if dist_from_logits and not fused_loss:
@@ -74,6 +84,20 @@ class RAINBOW(DQNPer):
         self.fused_loss = bool(fused_loss)
         self.dist_from_logits = bool(dist_from_logits)
         self.exact_nstep_bootstrap = bool(exact_nstep_bootstrap)
+        self.noisy_nets = bool(noisy_nets)
+        if self.noisy_nets:
+            for name, net in (("qnet", self.qnet),
+                              ("qnet_target", self.qnet_target)):
+                if not noisy_layers(net):
+                    raise ValueError(
+                        f"noisy_nets=True but {name} contains no "
+                        "NoisyLinear layer."
+                    )
+            # independent streams for the two nets, reproducible under
+            # torch.manual_seed
+            seed = int(t.randint(0, 2 ** 62, (1,)).item())
+            reset_noise(self.qnet, seed=seed)
+            reset_noise(self.qnet_target, seed=seed + 1)
 
     # ------------------------------------------------------------------
     def _criticize(self, state: Dict[str, Any], use_target: bool = False,
@@ -92,11 +116,22 @@ class RAINBOW(DQNPer):
         return (dist * support.view(1, 1, N)).sum(dim=2)
 
     def act_discrete(self, state, use_target=False, **__):
+        if self.noisy_nets:
+            net = self.qnet_target if use_target else self.qnet
+            with noise_enabled(net, False):
+                q = self._q_values(self._criticize(state, use_target))
+            return t.argmax(q, dim=1).view(-1, 1)
         q = self._q_values(self._criticize(state, use_target))
         return t.argmax(q, dim=1).view(-1, 1)
 
     def act_discrete_with_noise(self, state, use_target=False,
                                 decay_epsilon=True, **__):
+        if self.noisy_nets:
+            # exploration is the net's own noise: new noise, then the
+            # greedy action of every row
+            reset_noise(self.qnet_target if use_target else self.qnet)
+            q = self._q_values(self._criticize(state, use_target))
+            return t.argmax(q, dim=1).view(-1, 1)
         q = self._q_values(self._criticize(state, use_target))
         batch, n_actions = q.shape
         if t.rand(1).item() < self.epsilon:
@@ -215,6 +250,9 @@ class RAINBOW(DQNPer):
         if batch_size == 0:
             return 0.0
         self.qnet.train()
+        if self.noisy_nets:
+            reset_noise(self.qnet)
+            reset_noise(self.qnet_target)
 
         dist = self._criticize(state)  # [B, A, N]
         B, A, N = dist.shape
@@ -296,6 +334,7 @@ class RAINBOW(DQNPer):
         fc.setdefault("value_min", -10.0)
         fc.setdefault("value_max", 10.0)
         fc.setdefault("reward_future_steps", 3)
+        fc.setdefault("noisy_nets", False)
         return config
 
     @classmethod

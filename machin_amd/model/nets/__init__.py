@@ -5,6 +5,13 @@ from .base import (
 )
 from .gaussian import GaussianPolicyHead
 from .nature_cnn import ActorCriticCNN, NatureCNN, mlp
+from .noisy import (
+    NoisyDuelingC51Head,
+    NoisyLinear,
+    noise_enabled,
+    noisy_layers,
+    reset_noise,
+)
 from .resnet import ResNet
 
 __all__ = [
@@ -16,4 +23,9 @@ __all__ = [
     "mlp",
     "ResNet",
     "GaussianPolicyHead",
+    "NoisyLinear",
+    "NoisyDuelingC51Head",
+    "reset_noise",
+    "noise_enabled",
+    "noisy_layers",
 ]

@@ -680,6 +680,190 @@ def c51_loss(
     )
 
 
+# ======================================================================
+# NoisyLinear (factorised Gaussian noise) and its noise fill
+# ======================================================================
+# Largest batch (rows of x) the fused kernels take; above it the
+# two-GEMM torch form runs on the device. Set from the measured table in
+# docs/PERFORMANCE.md ("NoisyLinear").
+NOISY_LINEAR_FUSED_MAX_BATCH = 32
+
+
+def _noisy_linear_check(x, weight_mu, weight_sigma, bias_mu, bias_sigma,
+                        eps_in, eps_out, x_dtypes):
+    """Shared argument validation of :func:`noisy_linear`; returns
+    ``(I, O)``."""
+    if x.dtype not in x_dtypes:
+        raise ValueError("x must be float32 or bfloat16")
+    if weight_mu.dim() != 2:
+        raise ValueError("weight_mu must be [O, I]")
+    O, I = weight_mu.shape
+    if O < 1 or I < 1 or O * I >= 2 ** 31:
+        raise ValueError("need I, O >= 1 and O * I < 2^31")
+    if x.dim() < 1 or x.shape[-1] != I or x.numel() == 0:
+        raise ValueError(f"x must be [..., {I}] and not empty")
+    pdt = t.float64 if x.dtype == t.float64 else t.float32
+    for name, p, shape in (
+        ("weight_mu", weight_mu, (O, I)),
+        ("weight_sigma", weight_sigma, (O, I)),
+        ("bias_mu", bias_mu, (O,)),
+        ("bias_sigma", bias_sigma, (O,)),
+        ("eps_in", eps_in, (I,)),
+        ("eps_out", eps_out, (O,)),
+    ):
+        if tuple(p.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}")
+        if p.dtype != pdt:
+            raise ValueError(f"{name} must be {pdt}")
+        if p.device != x.device:
+            raise ValueError(f"{name} must be on x's device")
+    return I, O
+
+
+def _noisy_linear_torch(x, weight_mu, weight_sigma, bias_mu, bias_sigma,
+                        eps_in, eps_out):
+    """Torch composition of :func:`noisy_linear` in the two-GEMM form
+    ``x @ mu.T + ((x * eps_in) @ sigma.T) * eps_out + bias`` (the CPU
+    path, the device path above the fused batch limit and the reference
+    the kernels are timed against). Computes in fp32 and returns x's
+    dtype, also inside a ``torch.autocast`` region (autocast is switched
+    off for the two GEMMs); float64 inputs are accepted here (not by the
+    kernels) and computed in float64, for gradient checks."""
+    _noisy_linear_check(
+        x, weight_mu, weight_sigma, bias_mu, bias_sigma, eps_in, eps_out,
+        (t.float32, t.bfloat16, t.float64),
+    )
+    ct = t.float64 if x.dtype == t.float64 else t.float32
+    eps_in, eps_out = eps_in.detach(), eps_out.detach()
+    # inside an autocast region the GEMMs would round x and the weights
+    # to bf16; the op computes in fp32 like the kernels
+    with t.autocast(device_type=x.device.type, enabled=False):
+        xc = x.to(ct)
+        y = xc @ weight_mu.t() \
+            + ((xc * eps_in) @ weight_sigma.t()) * eps_out
+        y = y + (bias_mu + bias_sigma * eps_out)
+        return y.to(x.dtype)
+
+
+class _NoisyLinear(t.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight_mu, weight_sigma, bias_mu, bias_sigma,
+                eps_in, eps_out):
+        ext = _require_ext()
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        weight_mu = weight_mu.contiguous()
+        weight_sigma = weight_sigma.contiguous()
+        eps_in, eps_out = eps_in.contiguous(), eps_out.contiguous()
+        y = ext.noisy_linear_fwd(
+            x2, weight_mu, weight_sigma, bias_mu.contiguous(),
+            bias_sigma.contiguous(), eps_in, eps_out,
+        )
+        ctx.save_for_backward(x2, weight_mu, weight_sigma, eps_in, eps_out)
+        ctx.x_shape = x.shape
+        return y.view(*x.shape[:-1], weight_mu.shape[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        ext = _require_ext()
+        x2, weight_mu, weight_sigma, eps_in, eps_out = ctx.saved_tensors
+        g2 = g.reshape(-1, weight_mu.shape[0]).to(x2.dtype).contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.noisy_linear_bwd_input(
+                g2, weight_mu, weight_sigma, eps_in, eps_out
+            ).view(ctx.x_shape)
+        dmu = dsigma = dbias_mu = dbias_sigma = None
+        if any(ctx.needs_input_grad[1:5]):
+            dmu, dsigma, dbias_mu, dbias_sigma = ext.noisy_linear_bwd_weight(
+                g2, x2, eps_in, eps_out
+            )
+        return dx, dmu, dsigma, dbias_mu, dbias_sigma, None, None
+
+
+def noisy_linear(x: t.Tensor, weight_mu: t.Tensor, weight_sigma: t.Tensor,
+                 bias_mu: t.Tensor, bias_sigma: t.Tensor, eps_in: t.Tensor,
+                 eps_out: t.Tensor) -> t.Tensor:
+    """Linear layer with factorised Gaussian parameter noise (Fortunato
+    et al., "Noisy Networks for Exploration"): returns ``y [..., O]``.
+
+    ``x`` is ``[..., I]`` fp32 or bf16; ``weight_mu`` and
+    ``weight_sigma`` are fp32 ``[O, I]``, ``bias_mu``, ``bias_sigma``
+    and ``eps_out`` fp32 ``[O]``, ``eps_in`` fp32 ``[I]``;
+    ``O * I < 2^31``. All arithmetic is fp32, ``y`` takes ``x``'s dtype
+    with one rounding at the store::
+
+        w[o, i] = mu[o, i] + sigma[o, i] * eps_out[o] * eps_in[i]
+        y[b, o] = sum_i x[b, i] w[o, i] + bias_mu[o]
+                  + bias_sigma[o] * eps_out[o]
+
+    Differentiable in ``x`` and the four parameters (not in the noise)::
+
+        dx[b, i]       = sum_o dy[b, o] w[o, i]
+        dmu[o, i]      = sum_b dy[b, o] x[b, i]
+        dsigma[o, i]   = dmu[o, i] * eps_out[o] * eps_in[i]
+        dbias_mu[o]    = sum_b dy[b, o]
+        dbias_sigma[o] = dbias_mu[o] * eps_out[o]
+
+    On ROCm, up to ``NOISY_LINEAR_FUSED_MAX_BATCH`` rows this is one
+    gfx950 kernel per line above (machin_amd/ops/hip/noisy_linear.hip):
+    ``w`` is never stored, ``mu`` and ``sigma`` are read once forward and
+    once for ``dx``, and ``dmu`` / ``dsigma`` come out of one
+    accumulator. Sums have a fixed order, so results are reproducible
+    bit for bit. Larger batches, and CPU tensors, take the two-GEMM torch
+    form ``x @ mu.T + ((x * eps_in) @ sigma.T) * eps_out + bias``.
+    """
+    if not x.is_cuda:
+        return _noisy_linear_torch(
+            x, weight_mu, weight_sigma, bias_mu, bias_sigma, eps_in, eps_out
+        )
+    I, _ = _noisy_linear_check(
+        x, weight_mu, weight_sigma, bias_mu, bias_sigma, eps_in, eps_out,
+        (t.float32, t.bfloat16),
+    )
+    if x.numel() // I > NOISY_LINEAR_FUSED_MAX_BATCH:
+        return _noisy_linear_torch(
+            x, weight_mu, weight_sigma, bias_mu, bias_sigma, eps_in, eps_out
+        )
+    return _NoisyLinear.apply(
+        x, weight_mu, weight_sigma, bias_mu, bias_sigma,
+        eps_in.detach(), eps_out.detach(),
+    )
+
+
+def _factorised_noise_torch(buf: t.Tensor, seed: int, offset: int):
+    gen = t.Generator(device="cpu")
+    gen.manual_seed(
+        ((int(seed) * 0x9E3779B97F4A7C15) ^ (int(offset) * 0xD2511F53 + 1))
+        & 0x7FFFFFFFFFFFFFFF
+    )
+    z = t.randn(buf.numel(), generator=gen, dtype=t.float32)
+    buf.copy_((z.sign() * z.abs().sqrt()).view_as(buf))
+    return buf
+
+
+def factorised_noise_(buf: t.Tensor, seed: int, offset: int) -> t.Tensor:
+    """Fill the contiguous fp32 tensor ``buf`` in place with
+    ``f(z) = sign(z) sqrt(|z|)``, ``z ~ N(0, 1)`` (the factorised noise
+    of a NoisyLinear layer), and return it.
+
+    On ROCm this is one gfx950 kernel: element ``i`` is drawn from
+    Philox keyed by ``(seed, i, offset)``. On CPU the values come from a
+    ``torch.Generator`` seeded from ``(seed, offset)``. Each path is
+    reproducible for the same ``(seed, offset, buf.numel())``; the CPU
+    and the GPU streams do not match each other.
+    """
+    if buf.dtype != t.float32 or not buf.is_contiguous():
+        raise ValueError("buf must be a contiguous float32 tensor")
+    seed, offset = int(seed), int(offset)
+    if not (0 <= seed < 2 ** 63 and 0 <= offset < 2 ** 63):
+        raise ValueError("seed and offset must be in [0, 2^63)")
+    if not buf.is_cuda:
+        return _factorised_noise_torch(buf, seed, offset)
+    if buf.numel():
+        _require_ext().factorised_noise_(buf, seed, offset)
+    return buf
+
+
 class _PGHead(t.autograd.Function):
     @staticmethod
     def forward(ctx, logits, actions):
@@ -1251,6 +1435,8 @@ __all__ = [
     "categorical_projection",
     "categorical_policy_head",
     "c51_loss",
+    "noisy_linear",
+    "factorised_noise_",
     "FusedPolyak",
     "FusedRMSprop",
 ]

@@ -102,6 +102,21 @@ void bias_relu_flat_launch(const void*, const float*, void*, int64_t, int,
 void bias_relu_flat_bwd_launch(const void*, const void*, void*, float*,
                                float*, int64_t, int, int, hipStream_t);
 
+void noisy_linear_fwd_launch(const void*, const float*, const float*,
+                             const float*, const float*, const float*,
+                             const float*, void*, float*, int, int, int, int,
+                             int, bool, hipStream_t);
+void noisy_linear_bwd_input_launch(const void*, const float*, const float*,
+                                   const float*, const float*, void*, float*,
+                                   int, int, int, int, int, bool,
+                                   hipStream_t);
+void noisy_linear_bwd_weight_launch(const void*, const void*, const float*,
+                                    const float*, float*, float*, float*,
+                                    float*, int, int, int, bool, hipStream_t);
+void factorised_noise_launch(float*, int64_t, uint64_t, uint64_t,
+                             hipStream_t);
+int noisy_linear_slices(int64_t, int64_t, int64_t, int*);
+
 namespace {
 
 void check_f32_cuda(const Tensor& t, const char* name) {
@@ -295,6 +310,131 @@ Tensor categorical_projection(Tensor next_dist, Tensor rew, Tensor nd,
                                 (float)v_min, (float)v_max,
                                 current_stream());
   return out;
+}
+
+// ------------------------------------------------------------------
+// NoisyLinear (semantics: machin_amd.ops.noisy_linear)
+// ------------------------------------------------------------------
+// x or dy [B, cols] fp32 / bf16; mu, sigma [O, I]; eps_in [I], eps_out [O]
+void check_noisy(const Tensor& a, int64_t cols, const Tensor& mu,
+                 const Tensor& sigma, const Tensor& eps_in,
+                 const Tensor& eps_out, const char* name) {
+  TORCH_CHECK(a.is_cuda() && a.is_contiguous() && a.dim() == 2, name,
+              " must be a contiguous 2-D CUDA tensor");
+  TORCH_CHECK(a.scalar_type() == at::kFloat ||
+                  a.scalar_type() == at::kBFloat16,
+              name, " must be float32 or bfloat16");
+  TORCH_CHECK(mu.dim() == 2 && mu.size(0) >= 1 && mu.size(1) >= 1,
+              "weight_mu must be [O, I]");
+  const int64_t O = mu.size(0), I = mu.size(1);
+  TORCH_CHECK(O * I < ((int64_t)1 << 31), "O * I must be below 2^31");
+  TORCH_CHECK(a.size(0) >= 1 && a.size(0) <= 65535 * 32,
+              "batch must be in [1, 2097120]");
+  TORCH_CHECK(a.size(1) == cols, name, " has the wrong row length");
+  check_arg(mu, a, at::kFloat, O * I, "weight_mu");
+  check_arg(sigma, a, at::kFloat, O * I, "weight_sigma");
+  check_arg(eps_in, a, at::kFloat, I, "eps_in");
+  check_arg(eps_out, a, at::kFloat, O, "eps_out");
+}
+
+Tensor noisy_linear_fwd(Tensor x, Tensor mu, Tensor sigma, Tensor bias_mu,
+                        Tensor bias_sigma, Tensor eps_in, Tensor eps_out) {
+  TORCH_CHECK(mu.dim() == 2, "weight_mu must be [O, I]");
+  const int64_t O = mu.size(0), I = mu.size(1);
+  check_noisy(x, I, mu, sigma, eps_in, eps_out, "x");
+  check_arg(bias_mu, x, at::kFloat, O, "bias_mu");
+  check_arg(bias_sigma, x, at::kFloat, O, "bias_sigma");
+  const int64_t B = x.size(0);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({B, O}, x.options());
+  int cps = 1;
+  const int S = noisy_linear_slices(B, O, I, &cps);
+  Tensor part;
+  float* part_ptr = nullptr;
+  if (S > 1) {
+    part = at::empty({S, B, O}, x.options().dtype(at::kFloat));
+    part_ptr = part.data_ptr<float>();
+  }
+  noisy_linear_fwd_launch(
+      x.data_ptr(), mu.data_ptr<float>(), sigma.data_ptr<float>(),
+      bias_mu.data_ptr<float>(), bias_sigma.data_ptr<float>(),
+      eps_in.data_ptr<float>(), eps_out.data_ptr<float>(), y.data_ptr(),
+      part_ptr, (int)B, (int)I, (int)O, cps, S,
+      x.scalar_type() == at::kBFloat16, current_stream());
+  return y;
+}
+
+Tensor noisy_linear_bwd_input(Tensor dy, Tensor mu, Tensor sigma,
+                              Tensor eps_in, Tensor eps_out) {
+  TORCH_CHECK(mu.dim() == 2, "weight_mu must be [O, I]");
+  const int64_t O = mu.size(0), I = mu.size(1);
+  check_noisy(dy, O, mu, sigma, eps_in, eps_out, "dy");
+  const int64_t B = dy.size(0);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
+  Tensor dx = at::empty({B, I}, dy.options());
+  int cps = 1;
+  const int S = noisy_linear_slices(B, I, O, &cps);
+  Tensor part;
+  float* part_ptr = nullptr;
+  if (S > 1) {
+    part = at::empty({S, B, I}, dy.options().dtype(at::kFloat));
+    part_ptr = part.data_ptr<float>();
+  }
+  noisy_linear_bwd_input_launch(
+      dy.data_ptr(), mu.data_ptr<float>(), sigma.data_ptr<float>(),
+      eps_in.data_ptr<float>(), eps_out.data_ptr<float>(), dx.data_ptr(),
+      part_ptr, (int)B, (int)I, (int)O, cps, S,
+      dy.scalar_type() == at::kBFloat16, current_stream());
+  return dx;
+}
+
+// Returns {dmu [O, I], dsigma [O, I], dbias_mu [O], dbias_sigma [O]}.
+std::vector<Tensor> noisy_linear_bwd_weight(Tensor dy, Tensor x,
+                                            Tensor eps_in, Tensor eps_out) {
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 2,
+              "dy must be a contiguous 2-D CUDA tensor");
+  TORCH_CHECK(dy.scalar_type() == at::kFloat ||
+                  dy.scalar_type() == at::kBFloat16,
+              "dy must be float32 or bfloat16");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) == dy.size(0),
+              "x must be [B, I] with dy's batch");
+  const int64_t B = dy.size(0), O = dy.size(1), I = x.size(1);
+  TORCH_CHECK(B >= 1 && B < ((int64_t)1 << 31) && O >= 1 && I >= 1 &&
+                  O * I < ((int64_t)1 << 31) && O <= 65535 * 32,
+              "need B, I, O >= 1, O * I < 2^31 and O <= 2097120");
+  check_arg(x, dy, dy.scalar_type(), B * I, "x");
+  check_arg(eps_in, dy, at::kFloat, I, "eps_in");
+  check_arg(eps_out, dy, at::kFloat, O, "eps_out");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
+  const auto f32 = dy.options().dtype(at::kFloat);
+  Tensor dmu = at::empty({O, I}, f32);
+  Tensor dsigma = at::empty({O, I}, f32);
+  Tensor dbias_mu = at::empty({O}, f32);
+  Tensor dbias_sigma = at::empty({O}, f32);
+  noisy_linear_bwd_weight_launch(
+      dy.data_ptr(), x.data_ptr(), eps_in.data_ptr<float>(),
+      eps_out.data_ptr<float>(), dmu.data_ptr<float>(),
+      dsigma.data_ptr<float>(), dbias_mu.data_ptr<float>(),
+      dbias_sigma.data_ptr<float>(), (int)B, (int)I, (int)O,
+      dy.scalar_type() == at::kBFloat16, current_stream());
+  return {dmu, dsigma, dbias_mu, dbias_sigma};
+}
+
+// {slices S, steps per slice} of the forward / dx reduction for a
+// [B, N] output reduced over K: what the two launchers above use
+std::vector<int64_t> noisy_linear_slices_py(int64_t B, int64_t N,
+                                            int64_t K) {
+  TORCH_CHECK(B >= 1 && N >= 1 && K >= 1, "need B, N, K >= 1");
+  int cps = 1;
+  const int S = noisy_linear_slices(B, N, K, &cps);
+  return {S, cps};
+}
+
+void factorised_noise_(Tensor buf, int64_t seed, int64_t offset) {
+  check_f32_cuda(buf, "buf");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(buf.device());
+  factorised_noise_launch(buf.data_ptr<float>(), buf.numel(), (uint64_t)seed,
+                          (uint64_t)offset, current_stream());
 }
 
 // ------------------------------------------------------------------
@@ -1022,6 +1162,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("categorical_projection", &categorical_projection);
   m.def("c51_loss_fwd", &c51_loss_fwd);
   m.def("c51_loss_bwd", &c51_loss_bwd);
+  m.def("noisy_linear_fwd", &noisy_linear_fwd);
+  m.def("noisy_linear_bwd_input", &noisy_linear_bwd_input);
+  m.def("noisy_linear_bwd_weight", &noisy_linear_bwd_weight);
+  m.def("factorised_noise_", &factorised_noise_);
+  m.def("noisy_linear_slices", &noisy_linear_slices_py);
   m.def("multi_tensor_polyak", &multi_tensor_polyak);
   m.def("multi_tensor_polyak_cached", &multi_tensor_polyak_cached);
   m.def("fused_rmsprop_cached", &fused_rmsprop_cached);

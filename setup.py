@@ -25,6 +25,7 @@ SOURCES = [
     "scans.hip",
     "projection.hip",
     "c51_loss.hip",
+    "noisy_linear.hip",
     "multi_tensor.hip",
     "distributions.hip",
     "elementwise.hip",
