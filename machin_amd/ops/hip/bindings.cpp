@@ -890,18 +890,59 @@ void pixelcatch_reset(Tensor state, Tensor ball_no, Tensor mask, Tensor obs,
                           nhwc, current_stream());
 }
 
-std::vector<Tensor> conv1_wrw(Tensor dy, Tensor frames, double scale) {
-  // dy: [K, 32] bf16 (NHWC-flattened conv output grad);
-  // frames: [B, 84, 84, 4] u8. Returns [32, 4, 8, 8] fp32 grad.
-  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
-                  dy.is_contiguous() && dy.size(1) == 32,
-              "dy must be contiguous [K,32] bf16 CUDA");
+// Argument checks shared by the four stem conv entry points. The
+// kernels index a frame as 84 x 84 pixels of 4 bytes without looking at
+// the tensor's sizes, so anything else must stop here.
+void check_stem_frames(const Tensor& frames) {
   TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte &&
                   frames.is_contiguous(),
               "frames must be contiguous u8 CUDA");
+  TORCH_CHECK(frames.dim() == 4 && frames.size(1) == 84 &&
+                  frames.size(2) == 84 && frames.size(3) == 4,
+              "frames must be [B, 84, 84, 4] (NHWC)");
+}
+
+// weight: [256, 32] bf16 patch-major repack; bias: [32] fp32 or empty.
+// Both on the frames' device. Returns the bias pointer or nullptr.
+const float* check_stem_weight_bias(const Tensor& frames,
+                                    const Tensor& weight,
+                                    const Tensor& bias) {
+  TORCH_CHECK(weight.is_cuda() && weight.scalar_type() == at::kBFloat16 &&
+                  weight.is_contiguous() && weight.dim() == 2 &&
+                  weight.size(0) == 256 && weight.size(1) == 32,
+              "weight must be contiguous [256,32] bf16 CUDA");
+  TORCH_CHECK(weight.device() == frames.device(),
+              "weight must be on the frames' device");
+  if (!bias.defined() || bias.numel() == 0) return nullptr;
+  TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kFloat &&
+                  bias.is_contiguous() && bias.dim() == 1 &&
+                  bias.size(0) == 32,
+              "bias must be contiguous [32] fp32 CUDA, or empty");
+  TORCH_CHECK(bias.device() == frames.device(),
+              "bias must be on the frames' device");
+  return bias.data_ptr<float>();
+}
+
+void check_stem_dy(const Tensor& dy, const Tensor& frames) {
+  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
+                  dy.is_contiguous() && dy.dim() == 2 && dy.size(1) == 32,
+              "dy must be contiguous [K,32] bf16 CUDA");
+  check_stem_frames(frames);
+  TORCH_CHECK(frames.device() == dy.device(),
+              "frames must be on dy's device");
   TORCH_CHECK(dy.size(0) == frames.size(0) * 400,
               "K must equal batch*400");
+}
+
+std::vector<Tensor> conv1_wrw(Tensor dy, Tensor frames, double scale) {
+  // dy: [K, 32] bf16 (NHWC-flattened conv output grad);
+  // frames: [B, 84, 84, 4] u8. Returns [32, 4, 8, 8] fp32 grad.
+  check_stem_dy(dy, frames);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
+  if (dy.size(0) == 0) {  // no frames: zero gradients, nothing to launch
+    return {at::zeros({32, 4, 8, 8}, dy.options().dtype(at::kFloat)),
+            at::zeros({32}, dy.options().dtype(at::kFloat))};
+  }
   Tensor scratch = at::empty({32 * 256},
                              dy.options().dtype(at::kFloat));
   Tensor grad_w = at::empty({32, 4, 8, 8},
@@ -918,23 +959,13 @@ Tensor conv1_fwd(Tensor frames, Tensor weight, Tensor bias,
                  double scale) {
   // frames: [B, 84, 84, 4] u8 NHWC; weight: [256, 32] bf16 (patch-major
   // repack of the conv weight); bias: [32] fp32 or empty.
-  TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte &&
-                  frames.is_contiguous(),
-              "frames must be contiguous u8 CUDA");
-  TORCH_CHECK(weight.scalar_type() == at::kBFloat16 &&
-                  weight.is_contiguous() && weight.size(0) == 256 &&
-                  weight.size(1) == 32,
-              "weight must be contiguous [256,32] bf16");
+  check_stem_frames(frames);
+  const float* bias_ptr = check_stem_weight_bias(frames, weight, bias);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(frames.device());
   int64_t K = frames.size(0) * 400;
   Tensor out = at::empty({K, 32},
                          weight.options().dtype(at::kBFloat16));
-  const float* bias_ptr = nullptr;
-  if (bias.defined() && bias.numel() == 32) {
-    TORCH_CHECK(bias.scalar_type() == at::kFloat && bias.is_contiguous(),
-                "bias must be contiguous fp32");
-    bias_ptr = bias.data_ptr<float>();
-  }
+  if (K == 0) return out;  // no frames: nothing to launch
   conv1_fwd_launch(frames.data_ptr<unsigned char>(), weight.data_ptr(),
                    bias_ptr, out.data_ptr(), K, (float)scale,
                    current_stream());
@@ -945,25 +976,14 @@ Tensor conv1_fwd(Tensor frames, Tensor weight, Tensor bias,
 // bf16, sign mask [K] int32 (bit c of word k set <=> y[k][c] > 0)}.
 std::vector<Tensor> conv1_fwd_relu(Tensor frames, Tensor weight,
                                    Tensor bias, double scale) {
-  TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte &&
-                  frames.is_contiguous(),
-              "frames must be contiguous u8 CUDA");
-  TORCH_CHECK(weight.is_cuda() && weight.scalar_type() == at::kBFloat16 &&
-                  weight.is_contiguous() && weight.size(0) == 256 &&
-                  weight.size(1) == 32,
-              "weight must be contiguous [256,32] bf16 CUDA");
+  check_stem_frames(frames);
+  const float* bias_ptr = check_stem_weight_bias(frames, weight, bias);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(frames.device());
   int64_t K = frames.size(0) * 400;
   Tensor out = at::empty({K, 32},
                          weight.options().dtype(at::kBFloat16));
   Tensor mask = at::empty({K}, weight.options().dtype(at::kInt));
-  const float* bias_ptr = nullptr;
-  if (bias.defined() && bias.numel() == 32) {
-    TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kFloat &&
-                    bias.is_contiguous(),
-                "bias must be contiguous fp32 CUDA");
-    bias_ptr = bias.data_ptr<float>();
-  }
+  if (K == 0) return {out, mask};  // no frames: nothing to launch
   conv1_fwd_relu_launch(frames.data_ptr<unsigned char>(),
                         weight.data_ptr(), bias_ptr, out.data_ptr(),
                         (unsigned int*)mask.data_ptr<int>(), K,
@@ -976,21 +996,20 @@ std::vector<Tensor> conv1_fwd_relu(Tensor frames, Tensor weight,
 // clear are zeroed as they are loaded.
 std::vector<Tensor> conv1_wrw_masked(Tensor dy, Tensor mask, Tensor frames,
                                      double scale) {
-  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
-                  dy.is_contiguous() && dy.dim() == 2 && dy.size(1) == 32,
-              "dy must be contiguous [K,32] bf16 CUDA");
+  check_stem_dy(dy, frames);
   TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == at::kInt &&
                   mask.is_contiguous() && mask.dim() == 1 &&
                   mask.size(0) == dy.size(0),
               "mask must be contiguous [K] int32 CUDA");
+  TORCH_CHECK(mask.device() == dy.device(),
+              "mask must be on dy's device");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
+  if (dy.size(0) == 0) {  // no frames: zero gradients, nothing to launch
+    return {at::zeros({32, 4, 8, 8}, dy.options().dtype(at::kFloat)),
+            at::zeros({32}, dy.options().dtype(at::kFloat))};
+  }
   TORCH_CHECK((uintptr_t)mask.data_ptr() % 16 == 0,
               "mask must be 16-byte aligned");
-  TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte &&
-                  frames.is_contiguous(),
-              "frames must be contiguous u8 CUDA");
-  TORCH_CHECK(dy.size(0) == frames.size(0) * 400,
-              "K must equal batch*400");
-  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
   Tensor scratch = at::empty({32 * 256},
                              dy.options().dtype(at::kFloat));
   Tensor grad_w = at::empty({32, 4, 8, 8},

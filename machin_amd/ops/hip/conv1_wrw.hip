@@ -453,6 +453,18 @@ void conv1_fwd_launch(const unsigned char* frames, const void* weight,
 // x image: [nc 64][kq 8][4][4]  elem (k, c):
 //   addr = (c>>2)*128 + (k>>2)*16 + (k&3)*4 + (c&3)
 // dy image: [nc 8][kq 8][4][4] with the same windows.
+//
+// RETIRED, and corrected: the semantics above are incomplete. The later
+// probes (see the v3 header) showed that the 16 lanes of a quarter
+// receive only 16 distinct values, rows of the four subgroup leaders'
+// windows, so the read cannot deliver a 16x16x32 fragment. The exact
+// tests (tests/test_stem_conv_gpu.py) showed what that meant for these
+// kernels: every forward output and every weight-gradient element was
+// wrong, and the bias gradient held 4 distinct values per 16 channels
+// (channel c got the sum of channel c & 3 of its tile). The fragments
+// are now gathered from the same tiled images with plain LDS reads
+// (tile_frag below), which makes v2 correct and no faster than v1; the
+// transpose reads remain in the probes only.
 // =====================================================================
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
@@ -510,6 +522,19 @@ __device__ __forceinline__ void pack8(bf16x8& dst, bf16x4 lo, bf16x4 hi) {
     dst[j] = lo[j];
     dst[4 + j] = hi[j];
   }
+}
+
+// One lane's MFMA fragment from a [nc][kq][4][4] tiled image: `base`
+// points at k-quad 2g of the lane's n-cluster (g = lane >> 4); element j
+// is row k = 8g + j, column lane & 3 of the cluster, i.e. row j & 3 of
+// window j >> 2.
+__device__ __forceinline__ bf16x8 tile_frag(const __bf16* base, int lane) {
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    v[j] = base[(j >> 2) * 16 + (j & 3) * 4 + (lane & 3)];
+  }
+  return v;
 }
 
 __global__ __launch_bounds__(256)
@@ -620,13 +645,8 @@ void conv1_wrw_v2_kernel(const __bf16* __restrict__ dy,
     }
     __syncthreads();
 
-    // ---- fragments via transpose-reads ----------------------------
-    bf16x8 a_frag;
-    {
-      bf16x4 lo, hi;
-      ds_tr16_pair(a_base, lo, hi);
-      pack8(a_frag, lo, hi);
-    }
+    // ---- fragments from the tiled images -------------------------
+    bf16x8 a_frag = tile_frag(a_base, lane);
     // fused bias from the fragment already in registers: lane group g
     // of an ng==0 wave holds dy[k=8g..8g+7][col mt*16+(lane&15)]
     if (ng == 0) {
@@ -635,13 +655,7 @@ void conv1_wrw_v2_kernel(const __bf16* __restrict__ dy,
     }
 #pragma unroll
     for (int nt = 0; nt < 8; ++nt) {
-      const __bf16* bb = b_base + nt * 512;
-      bf16x8 b_frag;
-      {
-        bf16x4 lo, hi;
-        ds_tr16_pair(bb, lo, hi);
-        pack8(b_frag, lo, hi);
-      }
+      bf16x8 b_frag = tile_frag(b_base + nt * 512, lane);
       acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
           a_frag, b_frag, acc[nt], 0, 0, 0);
     }
@@ -666,9 +680,9 @@ void conv1_wrw_v2_kernel(const __bf16* __restrict__ dy,
   }
 }
 
-// fwd v2: weight staged ONCE into [nt 2][kt 64][4][16] tiles; the
-// B fragment becomes 2 transpose-reads per (pr) chunk, hoisted out of
-// the mt loop (v1 re-read it per element AND per m-tile).
+// fwd v2: weight staged ONCE into [nc 8][kq 64][4][4] windows; the
+// B fragment is gathered once per (pr) chunk, hoisted out of the mt
+// loop (v1 re-read it per m-tile).
 __global__ __launch_bounds__(256)
 void conv1_fwd_v2_kernel(const unsigned char* __restrict__ frames,
                          const __bf16* __restrict__ weight,  // [256][32]
@@ -743,13 +757,7 @@ void conv1_fwd_v2_kernel(const unsigned char* __restrict__ frames,
     __syncthreads();
 
     // B fragment for this pr chunk: k-quads pr*8 + {2g, 2g+1}
-    const __bf16* wb = w_base + pr * 8 * 16;
-    bf16x8 b_frag;
-    {
-      bf16x4 lo, hi;
-      ds_tr16_pair(wb, lo, hi);
-      pack8(b_frag, lo, hi);
-    }
+    bf16x8 b_frag = tile_frag(w_base + pr * 8 * 16, lane);
 #pragma unroll
     for (int mt2 = 0; mt2 < 2; ++mt2) {
       int m = wm * 32 + mt2 * 16 + (lane & 15);
