@@ -94,6 +94,21 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
     episode. Planes and transitions are both overwritten oldest first,
     so everything a live transition's window needs was written after
     its base plane and outlives it.
+
+    ``augment_shift = pad`` (1 to 16; 0, the default, is off) applies
+    the random shift of DrQ / RAD / data-efficient Rainbow to every
+    sampled batch: replicate-pad by ``pad`` and crop back at a random
+    offset, drawn independently for ``state`` and ``next_state`` and
+    shared by the ``k`` planes of a stack. Each ``sample_batch`` draws
+    one int32 ``[B, 4]`` tensor ``(dy_state, dx_state, dy_next,
+    dx_next)``, uniform on ``[-pad, pad]``, on the buffer's device from
+    that device's default generator (``t.manual_seed`` reproduces it; no
+    host read), and passes it as ``shift=`` to the gather op, so the
+    augmentation costs no extra pass over the pixels. The tensor comes
+    back as the custom attribute ``shift`` (under ``"*"``). Storing,
+    eviction, priorities and ``size()`` are unchanged and the ring
+    always holds the original frames. With ``augment_shift=0`` sampling
+    launches nothing more and returns no ``shift`` attribute.
     """
 
     def __init__(
@@ -107,9 +122,13 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
         validate: bool = True,
         n_step: int = 1,
         discount: float = 0.99,
+        augment_shift: int = 0,
         **per_kwargs,
     ):
         super().__init__(buffer_size, device, prioritized, **per_kwargs)
+        self.augment_shift = int(augment_shift)
+        if not 0 <= self.augment_shift <= 16:
+            raise ValueError("augment_shift must be in [0, 16].")
         self.frame_stack = int(frame_stack)
         if not 1 <= self.frame_stack <= 8:
             raise ValueError("frame_stack must be in [1, 8].")
@@ -406,6 +425,13 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
                 )
             else:
                 pos = self._uniform_live(batch_size)
+            shift = None
+            if self.augment_shift > 0:
+                pad = self.augment_shift
+                shift = t.randint(
+                    -pad, pad + 1, (batch_size, 4), dtype=t.int32,
+                    device=self.buffer_device,
+                )
             if self.n_step > 1:
                 # the kernel indexes these four ring columns itself
                 data = self._inner.data
@@ -421,6 +447,7 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
                     self._planes, *(data[k] for k in fused), pos,
                     self.frame_stack, self.n_step, self.discount,
                     channels_last=self.frame_layout == "nhwc",
+                    shift=shift,
                 )
                 cols["n_step"] = steps.view(-1, 1)
             else:
@@ -428,7 +455,10 @@ class DeviceFrameStackBuffer(DeviceTransitionBuffer):
                 state, next_state = ops.framestack_gather(
                     self._planes, cols.pop("_base"), self.frame_stack,
                     channels_last=self.frame_layout == "nhwc",
+                    shift=shift,
                 )
+            if shift is not None:
+                cols["shift"] = shift
             cols[self._state_col] = state
             cols[self._next_col] = next_state
             attrs = sample_attrs or (self._attr_order + ["*"])

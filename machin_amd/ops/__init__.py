@@ -937,8 +937,58 @@ def _framestack_gather_torch(
     )
 
 
+def _framestack_shift_stack(stack: t.Tensor, d: t.Tensor, fmt):
+    """``out[b, j, y, x] = stack[b, j, clamp(y + dy_b), clamp(x + dx_b)]``
+    with ``d = [B, 2]`` holding ``(dy, dx)``: one advanced-index gather."""
+    B, _, H, W = stack.shape
+    dev = stack.device
+    d = d.long()
+    # clamping d first does not change the result (the kernel does it
+    # to stay inside int32)
+    ys = (t.arange(H, device=dev).view(1, H)
+          + d[:, 0:1].clamp(-(H - 1), H - 1)).clamp(0, H - 1)
+    xs = (t.arange(W, device=dev).view(1, W)
+          + d[:, 1:2].clamp(-(W - 1), W - 1)).clamp(0, W - 1)
+    # indexed dims 0, 2, 3 around a slice: the result is [B, H, W, k]
+    out = stack[
+        t.arange(B, device=dev).view(B, 1, 1), :,
+        ys.view(B, H, 1), xs.view(B, 1, W),
+    ]
+    return out.permute(0, 3, 1, 2).contiguous(memory_format=fmt)
+
+
+def _framestack_check_shift(shift: t.Tensor, planes: t.Tensor, batch: int):
+    if not t.is_tensor(shift) or shift.dtype != t.int32:
+        raise ValueError("shift must be an int32 tensor")
+    if shift.device != planes.device:
+        raise ValueError("shift must be on the device of planes")
+    if shift.dim() != 2 or tuple(shift.shape) != (batch, 4):
+        raise ValueError("shift must be [B, 4]")
+    if not shift.is_contiguous():
+        raise ValueError("shift must be contiguous")
+
+
+def _framestack_gather_shift_torch(
+    planes: t.Tensor, base: t.Tensor, k: int, channels_last: bool,
+    shift: t.Tensor,
+):
+    """Torch composition of :func:`framestack_gather` with ``shift``
+    (the CPU path and the reference the kernel is tested and timed
+    against): the un-shifted composition, then one advanced-index
+    gather per stack."""
+    state, next_state = _framestack_gather_torch(
+        planes, base, k, channels_last
+    )
+    fmt = t.channels_last if channels_last else t.contiguous_format
+    return (
+        _framestack_shift_stack(state, shift[:, 0:2], fmt),
+        _framestack_shift_stack(next_state, shift[:, 2:4], fmt),
+    )
+
+
 def framestack_gather(
-    planes: t.Tensor, base: t.Tensor, k: int, channels_last: bool = False
+    planes: t.Tensor, base: t.Tensor, k: int, channels_last: bool = False,
+    shift: Optional[t.Tensor] = None,
 ):
     """Rebuild ``(state, next_state)`` frame stacks from a ring of
     frames stored once (frame-deduplicated replay).
@@ -953,6 +1003,21 @@ def framestack_gather(
     ``channels_last=True``, in ``torch.channels_last`` strides (memory
     ``[B, H, W, k]``, what the fused u8 conv stem consumes).
 
+    ``shift`` (int32 ``[B, 4]``, contiguous, on the device of
+    ``planes``) fuses the random-shift augmentation of DrQ / RAD into
+    the gather. Its columns are ``(dy_state, dx_state, dy_next,
+    dx_next)``; with ``S`` the stack returned without it::
+
+        out[b, j, y, x] = S[b, j, clamp(y + dy_b, 0, H-1),
+                                  clamp(x + dx_b, 0, W-1)]
+
+    one ``(dy, dx)`` for all ``k`` planes of a stack, ``state`` and
+    ``next_state`` shifted independently. For ``|d| <= pad`` this is
+    "replicate-pad by ``pad``, crop ``H x W`` at ``(pad + dy, pad +
+    dx)``"; it is defined for every int32 value (the kernel clamps
+    ``dy`` and ``dx`` before adding, which does not change the result).
+    ``shift=None`` is the un-shifted code path, call for call.
+
     On ROCm one gfx950 kernel loads each plane once per sample and
     writes both stacks (machin_amd/ops/hip/framestack.hip); the CPU
     fallback is the same semantics as a torch composition.
@@ -960,6 +1025,11 @@ def framestack_gather(
     k = int(k)
     if planes.is_cuda:
         ext = _require_ext()
+        if shift is not None:
+            state, next_state = ext.framestack_gather_shift(
+                planes, base, k, bool(channels_last), shift
+            )
+            return state, next_state
         state, next_state = ext.framestack_gather(
             planes, base, k, bool(channels_last)
         )
@@ -970,6 +1040,11 @@ def framestack_gather(
         raise ValueError("k must be in [1, 8]")
     if planes.shape[0] < k + 1:
         raise ValueError("ring needs at least k+1 planes")
+    if shift is not None:
+        _framestack_check_shift(shift, planes, base.numel())
+        return _framestack_gather_shift_torch(
+            planes, base, k, bool(channels_last), shift
+        )
     return _framestack_gather_torch(planes, base, k, bool(channels_last))
 
 
@@ -1013,10 +1088,32 @@ def _framestack_gather_nstep_torch(
     return stack(s), stack(s + m), acc, terminal_n, m
 
 
+def _framestack_gather_nstep_shift_torch(
+    planes: t.Tensor, base: t.Tensor, left: t.Tensor, reward: t.Tensor,
+    terminal: t.Tensor, pos: t.Tensor, k: int, n: int, gamma: float,
+    channels_last: bool, shift: t.Tensor,
+):
+    """Torch composition of :func:`framestack_gather_nstep` with
+    ``shift`` (the CPU path and the reference the kernel is tested and
+    timed against): the un-shifted composition, then one advanced-index
+    gather per stack. The three scalars are untouched."""
+    state, next_state, reward_n, terminal_n, steps = \
+        _framestack_gather_nstep_torch(
+            planes, base, left, reward, terminal, pos, k, n, gamma,
+            channels_last,
+        )
+    fmt = t.channels_last if channels_last else t.contiguous_format
+    return (
+        _framestack_shift_stack(state, shift[:, 0:2], fmt),
+        _framestack_shift_stack(next_state, shift[:, 2:4], fmt),
+        reward_n, terminal_n, steps,
+    )
+
+
 def framestack_gather_nstep(
     planes: t.Tensor, base: t.Tensor, left: t.Tensor, reward: t.Tensor,
     terminal: t.Tensor, pos: t.Tensor, k: int, n: int, gamma: float,
-    channels_last: bool = False,
+    channels_last: bool = False, shift: Optional[t.Tensor] = None,
 ):
     """:func:`framestack_gather` with n-step returns computed when
     sampling, from raw 1-step episodes: returns ``(state, next_state,
@@ -1049,6 +1146,11 @@ def framestack_gather_nstep(
     they are the stacks of ``framestack_gather(planes, base[pos], k)``
     and ``reward_n`` / ``terminal_n`` the stored values.
 
+    ``shift`` (int32 ``[B, 4]``) shifts the two stacks as in
+    :func:`framestack_gather`; ``reward_n``, ``terminal_n`` and
+    ``steps`` are unaffected, and ``shift=None`` is the un-shifted code
+    path, call for call.
+
     On ROCm the whole op is one gfx950 kernel launch
     (machin_amd/ops/hip/framestack.hip); the CPU fallback is the same
     semantics as a torch composition.
@@ -1056,6 +1158,11 @@ def framestack_gather_nstep(
     k, n = int(k), int(n)
     if planes.is_cuda:
         ext = _require_ext()
+        if shift is not None:
+            return tuple(ext.framestack_gather_nstep_shift(
+                planes, base, left, reward, terminal, pos, k, n,
+                float(gamma), bool(channels_last), shift,
+            ))
         return tuple(ext.framestack_gather_nstep(
             planes, base, left, reward, terminal, pos, k, n, float(gamma),
             bool(channels_last),
@@ -1081,6 +1188,12 @@ def framestack_gather_nstep(
         raise ValueError(
             "base, left, reward and terminal must be non-empty columns "
             "of the same length"
+        )
+    if shift is not None:
+        _framestack_check_shift(shift, planes, pos.numel())
+        return _framestack_gather_nstep_shift_torch(
+            planes, base, left, reward, terminal, pos, k, n, float(gamma),
+            bool(channels_last), shift,
         )
     return _framestack_gather_nstep_torch(
         planes, base, left, reward, terminal, pos, k, n, float(gamma),

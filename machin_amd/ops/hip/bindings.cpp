@@ -66,6 +66,15 @@ void framestack_gather_nstep_launch(
     const float*, const int64_t*, unsigned char*, unsigned char*, float*,
     float*, int64_t*, int64_t, int64_t, int64_t, int64_t, int, int, float,
     bool, hipStream_t);
+void framestack_gather_shift_launch(const unsigned char*, const int64_t*,
+                                    const int*, unsigned char*,
+                                    unsigned char*, int64_t, int64_t, int,
+                                    int, int, bool, hipStream_t);
+void framestack_gather_nstep_shift_launch(
+    const unsigned char*, const int64_t*, const int64_t*, const float*,
+    const float*, const int64_t*, const int*, unsigned char*,
+    unsigned char*, float*, float*, int64_t*, int64_t, int64_t, int64_t,
+    int, int, int, int, float, bool, hipStream_t);
 void pixelcatch_step_launch(int32_t*, int64_t*, const int64_t*,
                             unsigned char*, unsigned char*, float*, float*,
                             int32_t*, unsigned char*, int64_t*, float*,
@@ -703,8 +712,27 @@ Tensor u8_to_bf16_scale(Tensor in, double scale) {
 // [B, k, H, W] from a ring of u8 planes [P, H, W]; window plane j of
 // sample b is ring slot (base[b] + j) mod P. The kernel reduces base
 // modulo P itself, so values are never inspected on the host.
-std::vector<Tensor> framestack_gather(Tensor planes, Tensor base, int64_t k,
-                                      bool channels_last) {
+//
+// shift (may be null): int32 [B, 4] = (dy_state, dx_state, dy_next,
+// dx_next), the random-shift augmentation fused into the gather; null
+// launches exactly the un-shifted kernels.
+static void framestack_check_shift(const Tensor& shift,
+                                   const Tensor& planes, int64_t B) {
+  TORCH_CHECK(shift.is_cuda() && shift.device() == planes.device(),
+              "shift must be on the device of planes");
+  TORCH_CHECK(shift.scalar_type() == at::kInt, "shift must be int32");
+  TORCH_CHECK(shift.dim() == 2 && shift.size(0) == B && shift.size(1) == 4,
+              "shift must be [B, 4]");
+  TORCH_CHECK(shift.is_contiguous(), "shift must be contiguous");
+  TORCH_CHECK(planes.size(1) * planes.size(2) < (int64_t(1) << 30),
+              "shifted gather needs H * W < 2^30");
+}
+
+static std::vector<Tensor> framestack_gather_impl(const Tensor& planes,
+                                                  const Tensor& base,
+                                                  int64_t k,
+                                                  bool channels_last,
+                                                  const Tensor* shift) {
   TORCH_CHECK(planes.is_cuda() && planes.scalar_type() == at::kByte &&
                   planes.is_contiguous(),
               "planes must be contiguous uint8 CUDA");
@@ -719,10 +747,19 @@ std::vector<Tensor> framestack_gather(Tensor planes, Tensor base, int64_t k,
   TORCH_CHECK(P >= k + 1, "ring needs at least k+1 planes");
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(planes.device());
   const int64_t B = base.numel();
+  if (shift != nullptr) framestack_check_shift(*shift, planes, B);
   const auto fmt = channels_last ? at::MemoryFormat::ChannelsLast
                                  : at::MemoryFormat::Contiguous;
   Tensor state = at::empty({B, k, H, W}, planes.options(), fmt);
   Tensor next = at::empty({B, k, H, W}, planes.options(), fmt);
+  if (shift != nullptr) {
+    framestack_gather_shift_launch(
+        planes.data_ptr<unsigned char>(), base.data_ptr<int64_t>(),
+        shift->data_ptr<int>(), state.data_ptr<unsigned char>(),
+        next.data_ptr<unsigned char>(), B, P, (int)H, (int)W, (int)k,
+        channels_last, current_stream());
+    return {state, next};
+  }
   framestack_gather_launch(planes.data_ptr<unsigned char>(),
                            base.data_ptr<int64_t>(),
                            state.data_ptr<unsigned char>(),
@@ -731,16 +768,26 @@ std::vector<Tensor> framestack_gather(Tensor planes, Tensor base, int64_t k,
   return {state, next};
 }
 
+std::vector<Tensor> framestack_gather(Tensor planes, Tensor base, int64_t k,
+                                      bool channels_last) {
+  return framestack_gather_impl(planes, base, k, channels_last, nullptr);
+}
+
+std::vector<Tensor> framestack_gather_shift(Tensor planes, Tensor base,
+                                            int64_t k, bool channels_last,
+                                            Tensor shift) {
+  return framestack_gather_impl(planes, base, k, channels_last, &shift);
+}
+
 // n-step variant: the kernel indexes the whole transition-ring columns
 // base/left/reward/terminal [T] with the sampled positions pos [B] and
 // returns (state, next_state, reward_n, terminal_n, steps); semantics
 // in framestack.hip. All indices are reduced or clamped in the kernel.
-std::vector<Tensor> framestack_gather_nstep(Tensor planes, Tensor base,
-                                            Tensor left, Tensor reward,
-                                            Tensor terminal, Tensor pos,
-                                            int64_t k, int64_t n,
-                                            double gamma,
-                                            bool channels_last) {
+static std::vector<Tensor> framestack_gather_nstep_impl(
+    const Tensor& planes, const Tensor& base, const Tensor& left,
+    const Tensor& reward, const Tensor& terminal, const Tensor& pos,
+    int64_t k, int64_t n, double gamma, bool channels_last,
+    const Tensor* shift) {
   TORCH_CHECK(planes.is_cuda() && planes.scalar_type() == at::kByte &&
                   planes.is_contiguous(),
               "planes must be contiguous uint8 CUDA");
@@ -771,6 +818,7 @@ std::vector<Tensor> framestack_gather_nstep(Tensor planes, Tensor base,
               "base, left, reward and terminal must have the same length");
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(planes.device());
   const int64_t B = pos.numel();
+  if (shift != nullptr) framestack_check_shift(*shift, planes, B);
   const auto fmt = channels_last ? at::MemoryFormat::ChannelsLast
                                  : at::MemoryFormat::Contiguous;
   Tensor state = at::empty({B, k, H, W}, planes.options(), fmt);
@@ -778,6 +826,18 @@ std::vector<Tensor> framestack_gather_nstep(Tensor planes, Tensor base,
   Tensor reward_n = at::empty({B}, reward.options());
   Tensor terminal_n = at::empty({B}, reward.options());
   Tensor steps = at::empty({B}, pos.options());
+  if (shift != nullptr) {
+    framestack_gather_nstep_shift_launch(
+        planes.data_ptr<unsigned char>(), base.data_ptr<int64_t>(),
+        left.data_ptr<int64_t>(), reward.data_ptr<float>(),
+        terminal.data_ptr<float>(), pos.data_ptr<int64_t>(),
+        shift->data_ptr<int>(), state.data_ptr<unsigned char>(),
+        next.data_ptr<unsigned char>(), reward_n.data_ptr<float>(),
+        terminal_n.data_ptr<float>(), steps.data_ptr<int64_t>(), B, P, T,
+        (int)H, (int)W, (int)k, (int)n, (float)gamma, channels_last,
+        current_stream());
+    return {state, next, reward_n, terminal_n, steps};
+  }
   framestack_gather_nstep_launch(
       planes.data_ptr<unsigned char>(), base.data_ptr<int64_t>(),
       left.data_ptr<int64_t>(), reward.data_ptr<float>(),
@@ -787,6 +847,26 @@ std::vector<Tensor> framestack_gather_nstep(Tensor planes, Tensor base,
       steps.data_ptr<int64_t>(), B, P, T, H * W, (int)k, (int)n,
       (float)gamma, channels_last, current_stream());
   return {state, next, reward_n, terminal_n, steps};
+}
+
+std::vector<Tensor> framestack_gather_nstep(Tensor planes, Tensor base,
+                                            Tensor left, Tensor reward,
+                                            Tensor terminal, Tensor pos,
+                                            int64_t k, int64_t n,
+                                            double gamma,
+                                            bool channels_last) {
+  return framestack_gather_nstep_impl(planes, base, left, reward, terminal,
+                                      pos, k, n, gamma, channels_last,
+                                      nullptr);
+}
+
+std::vector<Tensor> framestack_gather_nstep_shift(
+    Tensor planes, Tensor base, Tensor left, Tensor reward, Tensor terminal,
+    Tensor pos, int64_t k, int64_t n, double gamma, bool channels_last,
+    Tensor shift) {
+  return framestack_gather_nstep_impl(planes, base, left, reward, terminal,
+                                      pos, k, n, gamma, channels_last,
+                                      &shift);
 }
 
 // batched device PixelCatch (pixelcatch.hip). Everything is written in
@@ -1197,6 +1277,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("u8_to_bf16_scale", &u8_to_bf16_scale);
   m.def("framestack_gather", &framestack_gather);
   m.def("framestack_gather_nstep", &framestack_gather_nstep);
+  m.def("framestack_gather_shift", &framestack_gather_shift);
+  m.def("framestack_gather_nstep_shift", &framestack_gather_nstep_shift);
   m.def("pixelcatch_step", &pixelcatch_step);
   m.def("pixelcatch_reset", &pixelcatch_reset);
   m.def("pg_head_fwd", &pg_head_fwd);

@@ -396,3 +396,265 @@ void framestack_gather_nstep_launch(
                      dim3(ma_grid(B * HW, block)), dim3(block), 0, stream,
                      planes, state, next, a, HW, k, nhwc);
 }
+
+// =====================================================================
+// Random-shift augmentation (DrQ / RAD) fused into both gathers.
+// shift is int32 [B, 4] = (dy_state, dx_state, dy_next, dx_next); with
+// S the stack the un-shifted gather returns,
+//   out[b, j, y, x] = S[b, j, clamp(y + dy, 0, H-1), clamp(x + dx, 0, W-1)]
+// which for |d| <= pad is "replicate-pad by pad, crop H x W at
+// (pad + dy, pad + dx)". One (dy, dx) per stack, all k planes. dy is
+// clamped into [-(H-1), H-1] and dx into [-(W-1), W-1] before the add
+// (same result), so no int32 value overflows or leaves a plane. Window
+// indices are reduced exactly as in the kernels above; the 1-step
+// gather is the n-step one with m = 1 and no scalars (NSTEP == false:
+// only a.base, a.B and a.P are set).
+//
+// - vector path (W % 4 == 0, 4 B aligned ring): one work item = one
+//   output dword = 4 pixels of one row of one sample, all planes of
+//   both stacks. The 4 source pixels clamp(x0 + q, 0, W-1), x0 = 4*xd +
+//   dx, always lie in the dword pair (a, min(a + 1, W/4 - 1)) with
+//   a = clamp(floor(x0 / 4), 0, W/4 - 1): an interior dword straddles
+//   two dwords, and a dword cut by a row end takes all its bytes from
+//   the row's first or last dword. So every output dword is two aligned
+//   dword loads and one v_perm_b32 whose byte selectors
+//   clamp(x0 + q, 0, W-1) - 4a (in [0, 7]) are computed once per stack:
+//   no branch, no byte loads.
+//     NCHW: one dword store per plane, consecutive lanes on
+//     consecutive dwords;
+//     NHWC, k == 4: 4 pixels x 4 channels = one dwordx4 store per
+//     stack through fs_transpose4.
+//   state and next_state have different shifts, so a plane they share
+//   is loaded once per stack; the second load comes from cache.
+// - scalar path (any other W, NHWC with k != 4): one pixel per item.
+// No LDS, no atomics, no scratch.
+// =====================================================================
+__device__ __forceinline__ int fs_clampi(int v, int lo, int hi) {
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+
+// where one stack's output dword (row y, dword xd) comes from: dword
+// offsets of the pair inside a plane and the v_perm_b32 selector
+struct fs_shift_src {
+  int lo, hi;
+  u32 sel;
+};
+
+__device__ __forceinline__ fs_shift_src fs_shift_dword(
+    const int* __restrict__ sh, int y, int xd, int H, int W) {
+  const int Wd = W >> 2;
+  const int dy = fs_clampi(sh[0], -(H - 1), H - 1);
+  const int dx = fs_clampi(sh[1], -(W - 1), W - 1);
+  const int ys = fs_clampi(y + dy, 0, H - 1);
+  const int x0 = 4 * xd + dx;  // |x0| < 2W
+  const int a = fs_clampi(x0 >> 2, 0, Wd - 1);
+  fs_shift_src r;
+  r.lo = ys * Wd + a;
+  r.hi = ys * Wd + (a + 1 < Wd ? a + 1 : Wd - 1);
+  r.sel = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    r.sel |= (u32)(fs_clampi(x0 + q, 0, W - 1) - 4 * a) << (8 * q);
+  return r;
+}
+
+__device__ __forceinline__ u32 fs_shift_load(const u32* __restrict__ plane,
+                                             const fs_shift_src& r) {
+  return __builtin_amdgcn_perm(plane[r.hi], plane[r.lo], r.sel);
+}
+
+// window of sample b: 1-step (base is indexed by b) or n-step
+template <bool NSTEP>
+__device__ __forceinline__ void fs_shift_window(const fs_nstep_args& a,
+                                                int64_t b, int64_t& p,
+                                                int64_t& s, int& m) {
+  if (NSTEP) {
+    fs_nstep_window(a, b, p, s, m);
+  } else {
+    p = b;
+    s = fs_base(a.base, b, a.P);
+    m = 1;
+  }
+}
+
+// NCHW vector path. C = H*W/4 dwords per plane; out dword c of channel
+// j of sample b is (b*K + j)*C + c.
+template <int K, bool NSTEP>
+__global__ void framestack_shift_nchw_vec_kernel(
+    const u32* __restrict__ planes, const int* __restrict__ shift,
+    u32* __restrict__ state, u32* __restrict__ next, fs_nstep_args a,
+    int H, int W) {
+  const int Wd = W >> 2;
+  const int64_t C = (int64_t)H * Wd;
+  const int64_t total = a.B * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / C;
+    const int c = (int)(i - b * C);
+    const int y = c / Wd, xd = c - y * Wd;
+    int64_t p, s;
+    int m;
+    fs_shift_window<NSTEP>(a, b, p, s, m);
+    const fs_shift_src rs = fs_shift_dword(shift + 4 * b, y, xd, H, W);
+    const fs_shift_src rn = fs_shift_dword(shift + 4 * b + 2, y, xd, H, W);
+    u32 v[K], w[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      v[j] = fs_shift_load(planes + fs_slot(s, j, a.P) * C, rs);
+      w[j] = fs_shift_load(planes + fs_slot(s, m + j, a.P) * C, rn);
+    }
+    const int64_t o = b * K * C + c;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      state[o + j * C] = v[j];
+      next[o + j * C] = w[j];
+    }
+    if (NSTEP && c == 0) fs_nstep_scalars(a, b, p, m);
+  }
+}
+
+// NHWC k == 4 vector path: item i owns uint4 i of each stack
+template <bool NSTEP>
+__global__ void framestack_shift_nhwc4_vec_kernel(
+    const u32* __restrict__ planes, const int* __restrict__ shift,
+    uint4* __restrict__ state, uint4* __restrict__ next, fs_nstep_args a,
+    int H, int W) {
+  const int Wd = W >> 2;
+  const int64_t C = (int64_t)H * Wd;
+  const int64_t total = a.B * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / C;
+    const int c = (int)(i - b * C);
+    const int y = c / Wd, xd = c - y * Wd;
+    int64_t p, s;
+    int m;
+    fs_shift_window<NSTEP>(a, b, p, s, m);
+    const fs_shift_src rs = fs_shift_dword(shift + 4 * b, y, xd, H, W);
+    const fs_shift_src rn = fs_shift_dword(shift + 4 * b + 2, y, xd, H, W);
+    u32 v[4], w[4], o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = fs_shift_load(planes + fs_slot(s, j, a.P) * C, rs);
+      w[j] = fs_shift_load(planes + fs_slot(s, m + j, a.P) * C, rn);
+    }
+    fs_transpose4(v[0], v[1], v[2], v[3], o);
+    state[i] = make_uint4(o[0], o[1], o[2], o[3]);
+    fs_transpose4(w[0], w[1], w[2], w[3], o);
+    next[i] = make_uint4(o[0], o[1], o[2], o[3]);
+    if (NSTEP && c == 0) fs_nstep_scalars(a, b, p, m);
+  }
+}
+
+// scalar path: one work item = one pixel of one sample
+template <bool NSTEP>
+__global__ void framestack_shift_scalar_kernel(
+    const u8* __restrict__ planes, const int* __restrict__ shift,
+    u8* __restrict__ state, u8* __restrict__ next, fs_nstep_args a, int H,
+    int W, int k, bool nhwc) {
+  const int64_t HW = (int64_t)H * W;
+  const int64_t total = a.B * HW;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / HW;
+    const int px = (int)(i - b * HW);
+    const int y = px / W, x = px - y * W;
+    int64_t p, s;
+    int m;
+    fs_shift_window<NSTEP>(a, b, p, s, m);
+    const int* sh = shift + 4 * b;
+    const int ps =
+        fs_clampi(y + fs_clampi(sh[0], -(H - 1), H - 1), 0, H - 1) * W +
+        fs_clampi(x + fs_clampi(sh[1], -(W - 1), W - 1), 0, W - 1);
+    const int pn =
+        fs_clampi(y + fs_clampi(sh[2], -(H - 1), H - 1), 0, H - 1) * W +
+        fs_clampi(x + fs_clampi(sh[3], -(W - 1), W - 1), 0, W - 1);
+    const int64_t o = nhwc ? i * k : b * k * HW + px;
+    const int64_t step = nhwc ? 1 : HW;
+    for (int j = 0; j < k; ++j) {
+      state[o + j * step] = planes[fs_slot(s, j, a.P) * HW + ps];
+      next[o + j * step] = planes[fs_slot(s, m + j, a.P) * HW + pn];
+    }
+    if (NSTEP && px == 0) fs_nstep_scalars(a, b, p, m);
+  }
+}
+
+template <int K, bool NSTEP>
+static void fs_launch_shift_nchw_vec(const u8* planes, const int* shift,
+                                     u8* state, u8* next,
+                                     const fs_nstep_args& a, int H, int W,
+                                     hipStream_t stream) {
+  const int block = 256;
+  hipLaunchKernelGGL((framestack_shift_nchw_vec_kernel<K, NSTEP>),
+                     dim3(ma_grid(a.B * H * (W / 4), block)), dim3(block), 0,
+                     stream, (const u32*)planes, shift, (u32*)state,
+                     (u32*)next, a, H, W);
+}
+
+// shared driver of the 1-step (NSTEP == false) and n-step launchers
+template <bool NSTEP>
+static void fs_shift_dispatch(const u8* planes, const int* shift, u8* state,
+                              u8* next, const fs_nstep_args& a, int H, int W,
+                              int k, bool nhwc, hipStream_t stream) {
+  const int block = 256;
+  const int64_t HW = (int64_t)H * W;
+  // rows are 4 B aligned when the ring is and W % 4 == 0; the NHWC
+  // path stores dwordx4
+  const bool vec =
+      (W % 4 == 0) && ((uintptr_t)planes & 3) == 0 &&
+      (((uintptr_t)state | (uintptr_t)next) & 15) == 0;
+  if (vec && !nhwc) {
+    switch (k) {
+      case 1: fs_launch_shift_nchw_vec<1, NSTEP>(planes, shift, state, next, a, H, W, stream); return;
+      case 2: fs_launch_shift_nchw_vec<2, NSTEP>(planes, shift, state, next, a, H, W, stream); return;
+      case 3: fs_launch_shift_nchw_vec<3, NSTEP>(planes, shift, state, next, a, H, W, stream); return;
+      case 4: fs_launch_shift_nchw_vec<4, NSTEP>(planes, shift, state, next, a, H, W, stream); return;
+      case 5: fs_launch_shift_nchw_vec<5, NSTEP>(planes, shift, state, next, a, H, W, stream); return;
+      case 6: fs_launch_shift_nchw_vec<6, NSTEP>(planes, shift, state, next, a, H, W, stream); return;
+      case 7: fs_launch_shift_nchw_vec<7, NSTEP>(planes, shift, state, next, a, H, W, stream); return;
+      case 8: fs_launch_shift_nchw_vec<8, NSTEP>(planes, shift, state, next, a, H, W, stream); return;
+      default: break;
+    }
+  }
+  if (vec && nhwc && k == 4) {
+    hipLaunchKernelGGL(framestack_shift_nhwc4_vec_kernel<NSTEP>,
+                       dim3(ma_grid(a.B * H * (W / 4), block)), dim3(block),
+                       0, stream, (const u32*)planes, shift, (uint4*)state,
+                       (uint4*)next, a, H, W);
+    return;
+  }
+  hipLaunchKernelGGL(framestack_shift_scalar_kernel<NSTEP>,
+                     dim3(ma_grid(a.B * HW, block)), dim3(block), 0, stream,
+                     planes, shift, state, next, a, H, W, k, nhwc);
+}
+
+// H * W < 2^30 is checked by the binding, so pixel offsets inside a
+// plane and 4 * xd + dx (< 2W) stay in int32
+void framestack_gather_shift_launch(const unsigned char* planes,
+                                    const int64_t* base, const int* shift,
+                                    unsigned char* state,
+                                    unsigned char* next, int64_t B,
+                                    int64_t P, int H, int W, int k,
+                                    bool nhwc, hipStream_t stream) {
+  if (B == 0 || H == 0 || W == 0) return;
+  const fs_nstep_args a = {base,    nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, B,       P,
+                           0,       1,       0.0f};
+  fs_shift_dispatch<false>(planes, shift, state, next, a, H, W, k, nhwc,
+                           stream);
+}
+
+void framestack_gather_nstep_shift_launch(
+    const unsigned char* planes, const int64_t* base, const int64_t* left,
+    const float* reward, const float* terminal, const int64_t* pos,
+    const int* shift, unsigned char* state, unsigned char* next,
+    float* reward_n, float* terminal_n, int64_t* steps, int64_t B,
+    int64_t P, int64_t T, int H, int W, int k, int n, float gamma,
+    bool nhwc, hipStream_t stream) {
+  if (B == 0) return;
+  const fs_nstep_args a = {base,     left,       reward, terminal, pos,
+                           reward_n, terminal_n, steps,  B,        P,
+                           T,        n,          gamma};
+  fs_shift_dispatch<true>(planes, shift, state, next, a, H, W, k, nhwc,
+                          stream);
+}

@@ -1,6 +1,7 @@
 """Time the frame-stack gather of the frame-deduplicated replay.
 
     python tools/bench_framestack.py [--out table.md] [--n-step N]
+        [--shift PAD]
 
 For 84x84 frames, k=4 and B in {32, 512, 4096}, in both output
 layouts, three ways of producing one sampled (state, next_state)
@@ -35,6 +36,21 @@ transition ring of ``--frames`` rows cut into episodes of 1000 steps
                  ``pos``), timed in the same rounds: the n-step
                  kernel's ratio to it is printed next to the ratio of
                  the plane bytes the two must move.
+
+With ``--shift PAD`` (PAD > 0) the table is about the random-shift
+augmentation fused into the gather (``shift=``), same shapes and
+method, one int32 ``[B, 4]`` draw uniform on ``[-PAD, PAD]`` per call;
+with ``--n-step N`` as well it is about the n-step op:
+
+* shifted kernel    — the op with ``shift=`` (one gfx950 kernel);
+* un-shifted kernel — the op without it on the same draws (equal plane
+                      bytes), timed in the same rounds: the ratio of the
+                      two is printed next to the max / min spread of the
+                      un-shifted kernel's rounds;
+* torch composition — ``ops._framestack_gather_shift_torch`` (or the
+                      n-step one) on the device: the un-shifted torch
+                      composition plus one advanced-index gather per
+                      stack, what a user would otherwise run.
 """
 import argparse
 import json
@@ -158,6 +174,99 @@ def nstep_table(args, dev):
     return lines
 
 
+def shift_table(args, dev):
+    """Rows for the shifted gathers (see the module docstring)."""
+    pad, n, gamma, L = args.shift, args.n_step, 0.99, 1000
+    P = T = args.frames
+    ring = t.randint(0, 256, (P, H, W), dtype=t.uint8, device=dev)
+    base = t.arange(T, device=dev)
+    left = (L - 1) - t.arange(T, device=dev) % L
+    reward = t.randn(T, device=dev)
+    terminal = (left == 0).float()
+    # plane bytes: the shift moves the bytes of the un-shifted kernel
+    planes = 3 * K + (min(n, K) if n > 1 else 1)
+
+    def gather(pos, nhwc, shift, torch_form=False):
+        if n > 1:
+            if torch_form:
+                return ops._framestack_gather_nstep_shift_torch(
+                    ring, base, left, reward, terminal, pos, K, n, gamma,
+                    nhwc, shift)
+            return ops.framestack_gather_nstep(
+                ring, base, left, reward, terminal, pos, K, n, gamma, nhwc,
+                shift=shift)
+        # base is the identity here, so base[pos] == pos
+        if torch_form:
+            return ops._framestack_gather_shift_torch(ring, pos, K, nhwc,
+                                                      shift)
+        return ops.framestack_gather(ring, pos, K, nhwc, shift=shift)
+
+    rows = []
+    for nhwc in (False, True):
+        variants = [
+            ("shift", lambda d: gather(d[0], nhwc, d[1])),
+            ("plain", lambda d: gather(d[0], nhwc, None)),
+            ("torch", lambda d: gather(d[0], nhwc, d[1], True)),
+        ]
+        for B in (32, 512, 4096):
+            draws = [
+                (t.randint(0, T, (B,), device=dev),
+                 t.randint(-pad, pad + 1, (B, 4), dtype=t.int32,
+                           device=dev))
+                for _ in range(16)
+            ]
+            pos, shift = draws[0]
+            want, got = gather(pos, nhwc, shift), gather(pos, nhwc, shift,
+                                                         True)
+            zero = gather(pos, nhwc, t.zeros_like(shift))
+            plain = gather(pos, nhwc, None)
+            for i in range(2):
+                assert t.equal(got[i], want[i])
+                assert got[i].stride() == want[i].stride()
+                assert t.equal(zero[i], plain[i])
+            for _, fn in variants:
+                time_ms(fn, draws, 20)  # warm-up
+            samples = {name: [] for name, _ in variants}
+            for _ in range(args.rounds):
+                for name, fn in variants:
+                    samples[name].append(time_ms(fn, draws, args.iters))
+            row = {"layout": "nhwc" if nhwc else "nchw", "B": B, "n": n,
+                   "pad": pad}
+            for name, vals in samples.items():
+                row[name + "_ms"] = statistics.median(vals)
+                row[name + "_min_ms"] = min(vals)
+                row[name + "_max_ms"] = max(vals)
+            row["shift_GBps"] = (
+                B * planes * H * W / (row["shift_ms"] * 1e-3) / 1e9
+            )
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+
+    what = f"n-step (n={n})" if n > 1 else "1-step"
+    lines = [
+        f"| layout | B | shifted {what} kernel ms (min-max), pad={pad} | "
+        "un-shifted kernel, same draws ms (min-max) | "
+        "torch composition ms | shifted kernel GB/s | "
+        "torch / shifted | shifted / un-shifted | "
+        "un-shifted max / min |",
+        "|---|---|---|---|---|---|---|---|---|",
+    ]
+    for r in rows:
+        lines.append(
+            f"| {r['layout']} | {r['B']} | {r['shift_ms']:.4f} "
+            f"({r['shift_min_ms']:.4f}-{r['shift_max_ms']:.4f}) | "
+            f"{r['plain_ms']:.4f} "
+            f"({r['plain_min_ms']:.4f}-{r['plain_max_ms']:.4f}) | "
+            f"{r['torch_ms']:.4f} "
+            f"({r['torch_min_ms']:.4f}-{r['torch_max_ms']:.4f}) | "
+            f"{r['shift_GBps']:.0f} | "
+            f"{r['torch_ms'] / r['shift_ms']:.2f}x | "
+            f"{r['shift_ms'] / r['plain_ms']:.3f} | "
+            f"{r['plain_max_ms'] / r['plain_min_ms']:.3f} |"
+        )
+    return lines
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--frames", type=int, default=65536,
@@ -169,11 +278,22 @@ def main():
     parser.add_argument("--out", default=None)
     parser.add_argument("--n-step", type=int, default=1,
                         help="> 1: time ops.framestack_gather_nstep")
+    parser.add_argument("--shift", type=int, default=0, metavar="PAD",
+                        help="> 0: time the shifted gathers (random-shift "
+                             "augmentation, draws uniform on [-PAD, PAD]); "
+                             "combines with --n-step")
     args = parser.parse_args()
     if not t.cuda.is_available():
         raise SystemExit("bench_framestack needs a GPU")
     dev = t.device("cuda:0")
     t.manual_seed(0)
+    if args.shift > 0:
+        table = "\n".join(shift_table(args, dev))
+        print(table)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(table + "\n")
+        return
     if args.n_step > 1:
         table = "\n".join(nstep_table(args, dev))
         print(table)
