@@ -14,6 +14,7 @@ __all__ = [
     "DistributedPrioritizedBuffer",
     "DeviceTransitionBuffer",
     "DeviceFrameStackBuffer",
+    "DeviceVecFrameStackBuffer",
     "default_buffer",
 ]
 
@@ -60,4 +61,8 @@ def __getattr__(name):
         from .frame_stack_buffer import DeviceFrameStackBuffer
 
         return DeviceFrameStackBuffer
+    if name == "DeviceVecFrameStackBuffer":
+        from .vec_frame_stack_buffer import DeviceVecFrameStackBuffer
+
+        return DeviceVecFrameStackBuffer
     raise AttributeError(name)

@@ -1202,6 +1202,183 @@ def framestack_gather_nstep(
 
 
 # ======================================================================
+# per-step vector-env store (machin_amd/ops/hip/framestack_vec.hip)
+# ======================================================================
+def _framestack_vec_check(planes, reward_col, terminal_col, left, head, run,
+                          frame, first, reward, terminal, done, fill, k, n):
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in [1, 8]")
+    if not 1 <= n <= 16:
+        raise ValueError("n must be in [1, 16]")
+    if not t.is_tensor(planes) or planes.dim() != 3 \
+            or planes.dtype != t.uint8 or not planes.is_contiguous():
+        raise ValueError("planes must be a contiguous uint8 [E*R, H, W] ring")
+    if not t.is_tensor(head) or head.dim() != 1 or head.numel() < 1:
+        raise ValueError("head must be [E] with E >= 1")
+    E, G = head.numel(), k + n
+    H, W = planes.shape[1:]
+    if H * W == 0 or planes.shape[0] % E != 0:
+        raise ValueError("planes must hold E non-empty rows")
+    R = planes.shape[0] // E
+    if R - G < 2 * G:
+        raise ValueError("lane_slots must be at least 2 * (k + n)")
+    for name, v, dtype, shape in (
+        ("reward column", reward_col, t.float32, (E * R,)),
+        ("terminal column", terminal_col, t.float32, (E * R,)),
+        ("left", left, t.int64, (E * R,)),
+        ("head", head, t.int64, (E,)),
+        ("run", run, t.int64, (E,)),
+        ("frame", frame, t.uint8, (E, H, W)),
+        ("first", first, t.uint8, (E, k, H, W)),
+        ("reward", reward, t.float32, (E,)),
+        ("terminal", terminal, t.float32, (E,)),
+        ("done", done, t.float32, (E,)),
+        ("fill", fill, t.float32, ()),
+    ):
+        if not t.is_tensor(v) or v.dtype != dtype:
+            raise ValueError(f"{name} must be a {dtype} tensor")
+        if tuple(v.shape) != shape:
+            raise ValueError(
+                f"{name} must be {list(shape)}, got {list(v.shape)}"
+            )
+        if v.device != planes.device:
+            raise ValueError(f"{name} must be on the device of planes")
+        if name != "first" and not v.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if not (first.is_contiguous()
+            or first.is_contiguous(memory_format=t.channels_last)):
+        raise ValueError(
+            "first must be contiguous or in channels_last strides"
+        )
+
+
+def _framestack_vec_append_torch(
+    planes: t.Tensor, reward_col: t.Tensor, terminal_col: t.Tensor,
+    left: t.Tensor, head: t.Tensor, run: t.Tensor, frame: t.Tensor,
+    first: t.Tensor, reward: t.Tensor, terminal: t.Tensor, done: t.Tensor,
+    fill: t.Tensor, k: int, n: int,
+):
+    """Torch composition of :func:`framestack_vec_append` (the CPU path
+    and the reference the kernel is tested against). Masked writes use
+    boolean indexing, so on a GPU it waits for the device."""
+    E, G = head.shape[0], k + n
+    R = planes.shape[0] // E
+    S = R - G
+    dev = planes.device
+    lane = t.arange(E, device=dev) * R
+
+    def write(column, slot, value, mask=None):
+        """value[e] at slot[e] of lane e's row, and at its mirror."""
+        idx = lane + slot
+        mirror = slot < G
+        if mask is not None:
+            idx, value, slot = idx[mask], value[mask], slot[mask]
+            mirror = mirror[mask]
+        column.index_copy_(0, idx, value)
+        column.index_copy_(0, idx[mirror] + S, value[mirror])
+
+    # python-style % is non-negative
+    i = head % S
+    bs = (i - k) % S
+    r = run + 1
+    ended = done != 0
+    write(planes, i, frame)
+    write(reward_col, bs, reward)
+    write(terminal_col, bs, terminal)
+    write(left, bs, t.zeros_like(i))
+    pos = lane + bs
+
+    dead = lane + i
+    leaf_idx = dead.view(E, 1).repeat(1, k + 1 + n)
+    leaf_w = t.zeros((E, k + 1 + n), dtype=t.float32, device=dev)
+    fill = fill.to(t.float32).expand(E)
+    zero = t.zeros(E, dtype=t.float32, device=dev)
+    for j in range(k):
+        slot = (i + 1 + j) % S
+        write(planes, slot, first[:, j], ended)
+        leaf_idx[:, 1 + j] = t.where(ended, lane + slot, dead)
+    for j in range(n):
+        # an ended episode: its last min(n, r) windows are complete
+        slot = (bs - j) % S
+        live = ended & (r > j)
+        write(left, slot, t.full_like(i, j), live)
+        leaf_idx[:, k + 1 + j] = t.where(live, lane + slot, dead)
+        leaf_w[:, k + 1 + j] = t.where(live, fill, zero)
+    # a running episode: the step completes the window n - 1 steps back
+    slot = (bs - (n - 1)) % S
+    live = ~ended & (r >= n)
+    write(left, slot, t.full_like(i, n - 1), live)
+    leaf_idx[:, k + 1] = t.where(live, lane + slot, leaf_idx[:, k + 1])
+    leaf_w[:, k + 1] = t.where(live, fill, leaf_w[:, k + 1])
+    head.copy_(t.where(ended, head + 1 + k, head + 1))
+    run.copy_(t.where(ended, t.zeros_like(r), r))
+    return pos, leaf_idx, leaf_w
+
+
+def framestack_vec_append(
+    planes: t.Tensor, reward_col: t.Tensor, terminal_col: t.Tensor,
+    left: t.Tensor, head: t.Tensor, run: t.Tensor, frame: t.Tensor,
+    first: t.Tensor, reward: t.Tensor, terminal: t.Tensor, done: t.Tensor,
+    fill: t.Tensor, k: int, n: int,
+):
+    """Store one step of ``E`` envs into the lane rings of
+    :class:`~machin_amd.frame.buffers.vec_frame_stack_buffer.DeviceVecFrameStackBuffer`;
+    returns ``(pos, leaf_idx, leaf_w)``.
+
+    Layout, with ``G = k + n`` and ``R = S + G``: ``planes`` u8
+    ``[E*R, H, W]`` is ``E`` rows of ``S`` ring slots followed by a
+    mirror of the row's first ``G`` slots; ``reward_col`` /
+    ``terminal_col`` (f32) and ``left`` (int64) are ``[E*R]`` columns
+    laid out the same way. "Slot ``i``" below means slot ``i`` of the
+    lane's row and, when ``i < G``, also slot ``S + i``. ``head`` and
+    ``run`` (int64 ``[E]``) are the planes a lane has written and the
+    transitions of its running episode. All six are updated in place.
+
+    Inputs of the step: ``frame`` u8 ``[E, H, W]`` (newest plane of the
+    next_state), ``first`` u8 ``[E, k, H, W]`` (contiguous or
+    ``channels_last``; the observation after the step, read only for
+    lanes whose episode ended), ``reward`` / ``terminal`` / ``done`` f32
+    ``[E]`` and ``fill``, a 0-dim f32 tensor. For lane ``e`` with ``i =
+    head[e] mod S``, ``bs = (i - k) mod S`` and ``r = run[e] + 1``
+    (slots modulo ``S``, non-negative, so no value of ``head``, ``run``
+    or ``done`` addresses outside the lane's row)::
+
+        plane i = frame[e]
+        reward, terminal, left at bs = reward[e], terminal[e], 0
+        pos[e] = e*R + bs;            leaf i -> 0
+        if done[e] != 0:
+            j < min(n, r):  left at bs-j = j;  leaf bs-j -> fill
+            j < k:          plane i+1+j = first[e, j];  leaf i+1+j -> 0
+            head[e] += 1 + k;  run[e] = 0
+        else:
+            r >= n:  left at bs-(n-1) = n-1;  leaf bs-(n-1) -> fill
+            head[e] += 1;  run[e] = r
+
+    The leaves are returned, not written: ``leaf_idx`` (int64) and
+    ``leaf_w`` (f32) are ``[E, k+1+n]`` with entry 0 the leaf of the
+    overwritten plane, entries ``1..k`` the zeroed leaves of an ended
+    lane's next first planes, entries ``k+1..k+n`` the filled leaves
+    (entry ``k+1+j`` is ``bs-j`` for an ended lane, entry ``k+1`` the
+    one filled leaf of a running lane); unused entries repeat ``(e*R +
+    i, 0)``, so duplicates carry equal weights and one
+    ``DeviceSumTree.update_leaf_batch`` applies the list. ``pos`` is
+    the flat position of the step's transition (where its action goes).
+
+    Needs ``S >= 2 * (k + n)``. On ROCm the op is one gfx950 kernel
+    launch, one workgroup per lane
+    (machin_amd/ops/hip/framestack_vec.hip); the CPU fallback is the
+    same semantics as a torch composition.
+    """
+    k, n = int(k), int(n)
+    args = (planes, reward_col, terminal_col, left, head, run, frame, first,
+            reward, terminal, done, fill)
+    _framestack_vec_check(*args, k, n)
+    if planes.is_cuda:
+        return tuple(_require_ext().framestack_vec_append(*args, k, n))
+    return _framestack_vec_append_torch(*args, k, n)
+
+
+# ======================================================================
 # batched device PixelCatch (machin_amd/ops/hip/pixelcatch.hip)
 # ======================================================================
 _PC_H = _PC_W = 84
@@ -1538,6 +1715,7 @@ __all__ = [
     "dequant_u8",
     "framestack_gather",
     "framestack_gather_nstep",
+    "framestack_vec_append",
     "pixelcatch_step",
     "pixelcatch_reset",
     "polyak_update_",

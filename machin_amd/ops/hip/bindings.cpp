@@ -75,6 +75,11 @@ void framestack_gather_nstep_shift_launch(
     const float*, const int64_t*, const int*, unsigned char*,
     unsigned char*, float*, float*, int64_t*, int64_t, int64_t, int64_t,
     int, int, int, int, float, bool, hipStream_t);
+void framestack_vec_append_launch(
+    unsigned char*, float*, float*, int64_t*, int64_t*, int64_t*,
+    const unsigned char*, const unsigned char*, const float*, const float*,
+    const float*, const float*, int64_t*, int64_t*, float*, int64_t, int64_t,
+    int64_t, int, int, bool, hipStream_t);
 void pixelcatch_step_launch(int32_t*, int64_t*, const int64_t*,
                             unsigned char*, unsigned char*, float*, float*,
                             int32_t*, unsigned char*, int64_t*, float*,
@@ -869,6 +874,70 @@ std::vector<Tensor> framestack_gather_nstep_shift(
                                       &shift);
 }
 
+// per-step store of a vector env into the lane rings of
+// DeviceVecFrameStackBuffer (framestack_vec.hip). The ring tensors,
+// head and run are written in place; returns (pos [E], leaf_idx
+// [E, k+1+n], leaf_w [E, k+1+n]). The kernel reduces every slot into
+// its lane's row itself, so values are never inspected on the host.
+std::vector<Tensor> framestack_vec_append(
+    Tensor planes, Tensor reward_col, Tensor terminal_col, Tensor left,
+    Tensor head, Tensor run, Tensor frame, Tensor first, Tensor reward,
+    Tensor terminal, Tensor done, Tensor fill, int64_t k, int64_t n) {
+  TORCH_CHECK(planes.is_cuda() && planes.scalar_type() == at::kByte &&
+                  planes.is_contiguous() && planes.dim() == 3,
+              "planes must be contiguous uint8 [E*R, H, W] CUDA");
+  TORCH_CHECK(k >= 1 && k <= 8, "k must be in [1, 8]");
+  TORCH_CHECK(n >= 1 && n <= 16, "n must be in [1, 16]");
+  TORCH_CHECK(head.dim() == 1 && head.numel() >= 1,
+              "head must be [E] with E >= 1");
+  const int64_t E = head.numel(), G = k + n;
+  const int64_t H = planes.size(1), W = planes.size(2), HW = H * W;
+  TORCH_CHECK(HW > 0, "planes must not be empty");
+  TORCH_CHECK(planes.size(0) % E == 0, "planes must hold E rows");
+  const int64_t R = planes.size(0) / E, S = R - G;
+  TORCH_CHECK(S >= 2 * G, "lane_slots must be at least 2 * (k + n)");
+  check_arg(reward_col, planes, at::kFloat, E * R, "reward column");
+  check_arg(terminal_col, planes, at::kFloat, E * R, "terminal column");
+  check_arg(left, planes, at::kLong, E * R, "left");
+  check_arg(head, planes, at::kLong, E, "head");
+  check_arg(run, planes, at::kLong, E, "run");
+  check_arg(frame, planes, at::kByte, E * HW, "frame");
+  check_arg(reward, planes, at::kFloat, E, "reward");
+  check_arg(terminal, planes, at::kFloat, E, "terminal");
+  check_arg(done, planes, at::kFloat, E, "done");
+  check_arg(fill, planes, at::kFloat, 1, "fill");
+  TORCH_CHECK(frame.dim() == 3 && frame.size(0) == E && frame.size(1) == H &&
+                  frame.size(2) == W,
+              "frame must be [E, H, W]");
+  TORCH_CHECK(first.is_cuda() && first.device() == planes.device() &&
+                  first.scalar_type() == at::kByte && first.dim() == 4 &&
+                  first.size(0) == E && first.size(1) == k &&
+                  first.size(2) == H && first.size(3) == W,
+              "first must be uint8 [E, k, H, W] on the ring's device");
+  bool first_nhwc = false;
+  if (!first.is_contiguous()) {
+    TORCH_CHECK(first.is_contiguous(at::MemoryFormat::ChannelsLast),
+                "first must be contiguous or in channels_last strides");
+    first_nhwc = true;
+  }
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(planes.device());
+  const int64_t L = k + 1 + n;
+  Tensor pos = at::empty({E}, head.options());
+  Tensor leaf_idx = at::empty({E, L}, head.options());
+  Tensor leaf_w = at::empty({E, L}, reward.options());
+  framestack_vec_append_launch(
+      planes.data_ptr<unsigned char>(), reward_col.data_ptr<float>(),
+      terminal_col.data_ptr<float>(), left.data_ptr<int64_t>(),
+      head.data_ptr<int64_t>(), run.data_ptr<int64_t>(),
+      frame.data_ptr<unsigned char>(), first.data_ptr<unsigned char>(),
+      reward.data_ptr<float>(), terminal.data_ptr<float>(),
+      done.data_ptr<float>(), fill.data_ptr<float>(),
+      pos.data_ptr<int64_t>(), leaf_idx.data_ptr<int64_t>(),
+      leaf_w.data_ptr<float>(), E, S, HW, (int)k, (int)n, first_nhwc,
+      current_stream());
+  return {pos, leaf_idx, leaf_w};
+}
+
 // batched device PixelCatch (pixelcatch.hip). Everything is written in
 // place; obs is [E, 4, 84, 84] u8, contiguous or in channels_last
 // strides. Returns whether obs was taken as NHWC.
@@ -1279,6 +1348,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("framestack_gather_nstep", &framestack_gather_nstep);
   m.def("framestack_gather_shift", &framestack_gather_shift);
   m.def("framestack_gather_nstep_shift", &framestack_gather_nstep_shift);
+  m.def("framestack_vec_append", &framestack_vec_append);
   m.def("pixelcatch_step", &pixelcatch_step);
   m.def("pixelcatch_reset", &pixelcatch_reset);
   m.def("pg_head_fwd", &pg_head_fwd);

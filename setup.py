@@ -30,6 +30,7 @@ SOURCES = [
     "distributions.hip",
     "elementwise.hip",
     "framestack.hip",
+    "framestack_vec.hip",
     "pixelcatch.hip",
     "conv1_wrw.hip",
     "bias_act.hip",
