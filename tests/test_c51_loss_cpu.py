@@ -4,7 +4,14 @@ built on it (``fused_loss``, ``dist_from_logits``,
 
 Tolerances: the fallback against the eager chain of ``RAINBOW.update``
 is the same fp32 arithmetic (``atol=1e-6``); against the float64
-reference ``rtol=1e-4, atol=1e-3``, the project's projection tolerance.
+reference ``rtol=1e-4, atol=1e-3``, the project's projection tolerance,
+in the older tests. That ``atol`` is the size of a typical element of
+``proj``, so ``TestHatReference`` holds the fallback (``loss``, ``proj``
+and the gradient) to the per-element worst-case rounding bound derived
+in ``util_c51_loss.reference_hat``, on every edge case and support of
+``util_c51_loss.EDGE_CASES``, and checks the bound itself: a typical
+bound is below 1/1000 of a typical element, and six deliberately wrong
+references differ from the true one by more than twice the bound.
 """
 import numpy as np
 import pytest
@@ -14,10 +21,12 @@ from machin_amd import ops
 from machin_amd.frame.algorithms import RAINBOW
 from machin_amd.frame.buffers import DeviceFrameStackBuffer
 from util_c51_loss import (
-    ATOL, RTOL, SMALL_SHAPES, V_MAX, V_MIN, FixedLogitsNet, LogitsQNet,
-    PixelDistQNet, build_rainbow, expected_logits_loss, make_case, op_args,
-    pixel_episode, record_update, reference64, seed_all, seeded_update,
-    shape_id,
+    ATOL, EDGE_CASES, RTOL, SMALL_SHAPES, V_MAX, V_MIN, WRONG_CASES,
+    WRONG_VARIANTS, FixedLogitsNet, LogitsQNet, PixelDistQNet,
+    build_rainbow, edge_id, edge_reference, expected_logits_loss,
+    fallback_edge_result, make_case, make_edge_case, make_tie_case, op_args,
+    pixel_episode, record_update, reference64, reference_hat, seed_all,
+    seeded_update, shape_id, taken_rows, worst_ratio,
 )
 
 SHAPE_IDS = [shape_id(s) for s in SMALL_SHAPES]
@@ -157,6 +166,105 @@ class TestFallback:
 
     def test_exported(self):
         assert "c51_loss" in ops.__all__
+
+
+# -- the hat-form reference and its bound ----------------------------------
+MODES = pytest.mark.parametrize("from_logits", [False, True],
+                                ids=["prob", "logits"])
+EDGE = pytest.mark.parametrize("case_key", EDGE_CASES,
+                               ids=[edge_id(c) for c in EDGE_CASES])
+OUTPUTS = ("loss", "proj", "grad")
+
+
+class TestHatReference:
+    @MODES
+    @EDGE
+    def test_agrees_with_reference64(self, case_key, from_logits):
+        case = make_edge_case(*case_key, t.float32, from_logits)
+        ref, _ = edge_reference(case_key, t.float32, from_logits)
+        want_loss, want_proj, want_best = reference64(case)
+        assert t.equal(ref.best, want_best) and t.equal(ref.best, case.best)
+        # float64 rounding: the two forms order the sums differently
+        assert float((ref.proj - want_proj).abs().max()) <= 1e-12
+        assert t.allclose(ref.loss, want_loss, rtol=1e-12, atol=1e-12)
+
+    @MODES
+    @pytest.mark.parametrize("shape", [(5, 3, 51), (9, 4, 124)],
+                             ids=shape_id)
+    def test_gradient_is_the_float64_autograd(self, shape, from_logits):
+        case = make_edge_case(shape, V_MIN, V_MAX, t.float32, from_logits)
+        ref, _ = edge_reference((shape, V_MIN, V_MAX), t.float32,
+                                from_logits)
+        args = list(op_args(case))
+        for i in (0, 2, 3):
+            args[i] = args[i].double()
+        args[0].requires_grad_(True)
+        loss, _, _ = ops._c51_loss_torch(*args, from_logits=from_logits)
+        (grad,) = t.autograd.grad(loss, args[0], case.g.double())
+        rows, others_zero = taken_rows(grad, case)
+        assert others_zero
+        assert t.allclose(rows, ref.grad, rtol=1e-10, atol=1e-12)
+
+    @MODES
+    @EDGE
+    def test_fallback_is_within_the_bound(self, case_key, from_logits):
+        """A condition on the bound: a second fp32 evaluation, in
+        another order than the kernel's, must fit under it."""
+        case = make_edge_case(*case_key, t.float32, from_logits)
+        ref, bound = edge_reference(case_key, t.float32, from_logits)
+        loss, proj, best, grad = fallback_edge_result(case)
+        rows, others_zero = taken_rows(grad, case)
+        assert others_zero
+        assert t.equal(best, ref.best)
+        for name, got in zip(OUTPUTS, (loss, proj, rows)):
+            ratio, ok = worst_ratio(got, getattr(ref, name),
+                                    getattr(bound, name))
+            print(f"{name} worst error/bound {ratio:.3g}")
+            assert ok, name
+
+    def test_bound_is_tight(self):
+        """The tightening over ``atol=1e-3``: on the (67, 18, 65)
+        logits case the median bound of ``proj`` is at most 1/1000 of
+        the median element of ``proj``, which itself is only a few
+        times ``atol``."""
+        ref, bound = reference_hat(make_case((67, 18, 65), t.float32, True))
+        median = float(ref.proj.median())
+        assert 0.0 < median < 10 * ATOL
+        assert float(bound.proj.median()) <= median / 1000
+        # the edge case of that shape has more empty bins than filled
+        # ones; among the filled ones the same holds
+        ref, bound = edge_reference(((67, 18, 65), V_MIN, V_MAX),
+                                    t.float32, True)
+        filled = ref.proj > 0
+        assert float(bound.proj[filled].median()) \
+            <= float(ref.proj[filled].median()) / 1000
+
+    @MODES
+    @pytest.mark.parametrize("case_key", WRONG_CASES,
+                             ids=[edge_id(c) for c in WRONG_CASES])
+    def test_wrong_references_exceed_the_bound(self, case_key, from_logits):
+        """Each wrong variant of the reference differs from the true one
+        by more than twice the bound somewhere, so a result within the
+        bound of the truth (the fallback above, the kernel on the
+        device) cannot be within the bound of a variant. Dropping ``S``
+        from the logits gradient is left out: ``S = sum(proj)`` is 1
+        here, so that is not observable."""
+        case = make_edge_case(*case_key, t.float32, from_logits)
+        ref, bound = edge_reference(case_key, t.float32, from_logits)
+        for variant in WRONG_VARIANTS:
+            wrong, _ = reference_hat(case, wrong=variant)
+            seen = False
+            for name in OUTPUTS:
+                gap = (getattr(wrong, name) - getattr(ref, name)).abs()
+                seen |= bool((gap > 2 * getattr(bound, name)).any())
+            assert seen, variant
+
+    @MODES
+    def test_tie_goes_to_the_lower_action(self, from_logits):
+        case = make_tie_case(t.float32, from_logits)
+        _, _, best = ops.c51_loss(*op_args(case), from_logits=from_logits)
+        assert t.equal(best, case.best)
+        assert t.equal(reference_hat(case)[0].best, case.best)
 
 
 # -- RAINBOW ---------------------------------------------------------------

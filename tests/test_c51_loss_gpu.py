@@ -11,7 +11,38 @@ compared exactly. Rows of ``proj`` sum to the mass of the projected
 row within ``1e-5``: 1 for logits and fp32 probabilities; a probability
 row stored in bf16 sums to 1 only within ``2^-9``, and the projection
 keeps whatever mass it is given.
+
+That ``atol`` is the size of a typical element of ``proj`` and of the
+fp32 gradient, so ``TestAgainstHatReference`` holds ``loss``, ``proj``
+and the taken row of the gradient, element by element, to the
+worst-case fp32 rounding bound derived in
+``util_c51_loss.reference_hat`` against its float64 hat-form reference
+(a bf16 gradient adds ``2^-8 |ref|``), on every shape and support of
+``util_c51_loss.EDGE_CASES``; ``best`` and the rows of untaken actions
+are exact. The CPU module checks the bound itself.
+
+MEASURED on one MI355X, the kernels' worst error / bound over all of
+``EDGE_CASES``::
+
+    mode    dtype  loss   proj   grad
+    prob    fp32   0.092  0.394  0.394
+    prob    bf16   0.104  0.394  0.984
+    logits  fp32   0.094  0.394  0.392
+    logits  bf16   0.087  0.394  0.991
+
+    tie rows (fp32 and bf16)         0.009  0.166  0.96
+    scalar discount 0.0, fp32        0.030  0.22   0.22
+    scalar discount 1.0, fp32        0.026  0.22   0.22
+
+``proj`` and the fp32 gradients peak on (33, 6, 256) over (-1, 1), the
+bf16 gradients and most losses on (8200, 3, 51); the fp32 CPU fallback
+reaches 0.39 on the same case as the kernels. ``2^-8`` is the
+unit roundoff of bf16 (round to nearest even errs by up to ``2^-8 /
+(1 + 2^-8)`` relative), so a bf16 gradient close to 1 is the rounding
+of the store among 1.25 million elements, not fp32 error.
 """
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 import torch as t
@@ -26,10 +57,11 @@ from machin_amd import ops  # noqa: E402
 from machin_amd.frame.algorithms import RAINBOW  # noqa: E402
 from machin_amd.frame.buffers import DeviceFrameStackBuffer  # noqa: E402
 from util_c51_loss import (  # noqa: E402
-    ALL_SHAPES, ATOL, BACKWARD_SHAPES, RTOL, V_MAX, V_MIN, FixedLogitsNet,
-    LogitsQNet, build_rainbow, expected_logits_loss, fallback_result,
-    make_case, op_args, pixel_episode, record_update, seeded_update,
-    shape_id,
+    ALL_SHAPES, ATOL, BACKWARD_SHAPES, EDGE_CASES, RTOL, V_MAX, V_MIN,
+    FixedLogitsNet, LogitsQNet, build_rainbow, edge_id, edge_reference,
+    expected_logits_loss, fallback_result, make_case, make_edge_case,
+    make_tie_case, op_args, pixel_episode, record_update, reference_hat,
+    seeded_update, shape_id, taken_rows, worst_ratio,
 )
 
 DEV = "cuda:0"
@@ -234,6 +266,112 @@ class TestBackward:
         else:
             assert t.allclose(got, want.bfloat16().float(),
                               rtol=2.0 ** -7, atol=1e-6)
+
+
+# -- the kernels against the hat-form reference and its bound --------------
+def run_device(case, discount=None):
+    """Forward and backward of the kernels on a case: ``(loss, proj,
+    best, grad [B, A, N])`` on the device."""
+    args = list(op_args(case, DEV, discount=discount))
+    args[0] = args[0].clone().requires_grad_(True)
+    loss, proj, best = ops.c51_loss(*args, from_logits=case.from_logits)
+    (grad,) = t.autograd.grad(loss, args[0], case.g.to(DEV))
+    return loss.detach(), proj, best, grad
+
+
+def within_bound(case, result, what, shared=True):
+    """Every output of ``result`` against the hat-form reference of a
+    case (the shared one of an unmodified edge case) and its bound;
+    prints the worst error/bound of each."""
+    ref, bound = edge_reference(
+        (case.shape, case.v_min, case.v_max), case.dtype, case.from_logits
+    ) if shared else reference_hat(case)
+    loss, proj, best, grad = (x.cpu() for x in result)
+    assert grad.dtype == case.dtype and grad.shape == case.dist.shape
+    assert loss.dtype == proj.dtype == t.float32
+    rows, others_zero = taken_rows(grad, case)
+    ok = others_zero and t.equal(best, ref.best)
+    for name, got in (("loss", loss), ("proj", proj), ("grad", rows)):
+        ratio, inside = worst_ratio(got, getattr(ref, name),
+                                    getattr(bound, name))
+        print(f"{what} {name} worst error/bound {ratio:.3g}")
+        ok = ok and inside
+    # the projection conserves the mass of the row it projects
+    nd = case.next_target.double()[t.arange(case.shape[0]), ref.best]
+    mass = t.ones(case.shape[0], dtype=t.float64) if case.from_logits \
+        else nd.sum(dim=1)
+    conserved = float((proj.double().sum(dim=1) - mass).abs().max()) <= 1e-5
+    return ok and conserved
+
+
+def with_discount(case, value):
+    """A copy of a case with every discount set to ``value``."""
+    copy = SimpleNamespace(**vars(case))
+    copy.discount = t.full_like(case.discount, value)
+    return copy
+
+
+class TestAgainstHatReference:
+    @MODES
+    @DTYPES
+    @pytest.mark.parametrize("case_key", EDGE_CASES,
+                             ids=[edge_id(c) for c in EDGE_CASES])
+    def test_within_the_bound(self, case_key, dtype, from_logits):
+        case = make_edge_case(*case_key, dtype, from_logits)
+        mode = "logits" if from_logits else "prob"
+        name = "bf16" if dtype == t.bfloat16 else "fp32"
+        assert within_bound(case, run_device(case),
+                            f"{mode} {name} {edge_id(case_key)}")
+
+    @MODES
+    @DTYPES
+    def test_tie_goes_to_the_lower_action(self, dtype, from_logits):
+        case = make_tie_case(dtype, from_logits)
+        result = run_device(case)
+        assert t.equal(result[2].cpu(), case.best)
+        assert within_bound(case, result, "tie", shared=False)
+
+    @MODES
+    @pytest.mark.parametrize("gamma", [0.0, 1.0])
+    def test_scalar_discounts_zero_and_one(self, gamma, from_logits):
+        case = with_discount(
+            make_edge_case((67, 18, 65), V_MIN, V_MAX, t.float32,
+                           from_logits), gamma)
+        scalar = run_device(case, discount=gamma)
+        tensor = run_device(case)
+        for a, b in zip(scalar, tensor):
+            assert t.equal(a, b)
+        assert within_bound(case, scalar, f"scalar discount {gamma:g}",
+                            shared=False)
+
+    @MODES
+    @pytest.mark.parametrize("where", ["reward", "next_target", "dist"])
+    def test_nan_stays_in_its_row(self, where, from_logits):
+        """Nine rows are three blocks of four waves that share one LDS
+        array: row 5 sits between rows 4, 6 and 7 of its block. Only
+        values are poisoned; every index the kernels form is clamped
+        (NaN positions go through fminf/fmaxf to bin 0, actions and
+        ``best`` are clamped), so no address depends on the NaN."""
+        src = make_edge_case((9, 4, 124), V_MIN, V_MAX, t.float32,
+                             from_logits)
+        b = 5
+        case = SimpleNamespace(**vars(src))
+        nan = float("nan")
+        if where == "reward":
+            case.reward = src.reward.clone()
+            case.reward[b] = nan
+        elif where == "next_target":
+            case.next_target = src.next_target.clone()
+            case.next_target[b, int(src.best[b]), 3] = nan
+        else:
+            case.dist = src.dist.clone()
+            case.dist[b, int(src.action[b]), 3] = nan
+        clean, dirty = run_device(src), run_device(case)
+        assert bool(t.isnan(dirty[0][b]))
+        others = t.tensor([i for i in range(9) if i != b], device=DEV)
+        for a, d in zip(clean, dirty):
+            assert t.equal(a[others], d[others])
+        assert not bool(t.isnan(clean[0]).any())
 
 
 # -- RAINBOW on the device -------------------------------------------------
