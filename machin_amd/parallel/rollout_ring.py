@@ -15,8 +15,26 @@ them.
 """
 from typing import Dict, List, Tuple
 
+import ctypes
+import os
+
 import torch as t
 import torch.multiprocessing as mp
+
+
+def _clear_last_hip_error():
+    """Read, and thereby reset, the calling thread's last HIP error.
+
+    The runtime keeps the error of a failed call until it is read, and
+    the next launch check would report it as its own. torch's runtime
+    bindings do not expose hipGetLastError, so it is called in the HIP
+    runtime that torch has loaded (its bundled one when there is one)."""
+    bundled = os.path.join(os.path.dirname(t.__file__), "lib",
+                           "libamdhip64.so")
+    hip = ctypes.CDLL(bundled if os.path.exists(bundled)
+                      else "libamdhip64.so")
+    hip.hipGetLastError.restype = ctypes.c_int
+    hip.hipGetLastError()
 
 
 class RolloutRing:
@@ -104,18 +122,33 @@ class RolloutRing:
         """Learner-side: hipHostRegister the shared-memory buffers so
         H2D copies DMA STRAIGHT from the ring slots (no host staging
         copy at all). Returns False when registration is unavailable
-        (callers then use pinned staging via :meth:`gather`)."""
+        (callers then use pinned staging via :meth:`gather`).
+
+        A refused registration leaves nothing behind: buffers that
+        were registered before the refusal are unregistered again, and
+        the error the runtime recorded for the refused call is cleared,
+        so the fall-back path's first copy does not report it."""
         try:
             cudart = t.cuda.cudart()
+        except Exception:  # noqa: BLE001 - optional fast path
+            return False
+        done = []
+        try:
             for buf in self.data.values():
                 rc = cudart.cudaHostRegister(
                     buf.data_ptr(), buf.numel() * buf.element_size(), 0
                 )
                 if int(rc) != 0:
-                    return False
-            return True
+                    break
+                done.append(buf)
+            else:
+                return True
         except Exception:  # noqa: BLE001 - optional fast path
-            return False
+            pass
+        for buf in done:
+            cudart.cudaHostUnregister(buf.data_ptr())
+        _clear_last_hip_error()
+        return False
 
     def upload_slots(
         self,

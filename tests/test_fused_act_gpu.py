@@ -286,7 +286,7 @@ def _reference_forward(params, frames):
 
 
 class TestWholeModel:
-    def test_matches_unfused_composition(self):
+    def test_matches_unfused_composition(self, monkeypatch):
         from machin_amd.model.nets.nature_cnn import FusedActorCriticCNN
 
         B = 6
@@ -314,6 +314,18 @@ class TestWholeModel:
             return ((logits.float() * g_logits).sum()
                     + (values.float() * g_values).sum())
 
+        # Both sides hand conv2/conv3 the same inputs and output
+        # gradients, so their weight gradients are two runs of one
+        # MIOpen call. Its default solver sums split-K partials with
+        # fp32 atomics and then rounds to bf16, so two runs can land on
+        # neighbouring bf16 values (measured: one to four elements, in
+        # 15 of 40 runs for conv2), a step far above ATOMIC_RTOL, which
+        # is sized for gradients kept in fp32. Asking MIOpen for its
+        # deterministic solvers makes the two runs one computation, and
+        # the bound holds as it stands; the default solvers are
+        # compared, to one bf16 step, in
+        # TestBiasRelu.test_module_matches_conv_bias_relu.
+        monkeypatch.setattr(t.backends.cudnn, "deterministic", True)
         logits, values = net(frames)
         ref_logits, ref_values = _reference_forward(params, frames)
         assert t.equal(logits, ref_logits)

@@ -1,5 +1,6 @@
 """RolloutRing: actor processes write shared-memory slots; the
 consumer drains, gathers and recycles."""
+import pytest
 import torch as t
 import torch.multiprocessing as mp
 
@@ -55,6 +56,39 @@ class TestRolloutRing:
         for p in procs:
             p.join(timeout=10)
         assert seen_values == {1, 2, 3}
+
+    @pytest.mark.gpu
+    def test_host_register_leaves_no_error(self):
+        """Whether or not the runtime accepts the registration, the
+        copies that follow it succeed and carry the slots' contents:
+        a refused hipHostRegister must not hand its error to them."""
+        ring = RolloutRing(slots=4, spec=SPEC)
+        for i in range(4):
+            slot = ring.slot(i)
+            slot["frames"].fill_(i + 1)
+            slot["rewards"].fill_(float(i + 1))
+        device = t.device("cuda")
+        idx = [2, 0, 3]
+        want = {k: v[idx] for k, v in ring.data.items()}
+        registered = ring.host_register()
+        if registered:
+            pool = {
+                k: t.zeros((4, *shape), dtype=dtype, device=device)
+                for k, (shape, dtype) in SPEC.items()
+            }
+            ring.upload_slots(idx, pool, [0, 1, 2])
+            got = {k: v[:3] for k, v in pool.items()}
+        else:
+            got = ring.gather(
+                idx, device, pinned=ring.make_pinned_staging(4)
+            )
+        t.cuda.synchronize()
+        for k in SPEC:
+            assert t.equal(got[k].cpu(), want[k])
+        # a kernel launch is checked against the last error as well
+        assert float((got["rewards"] + 1).sum()) == float(
+            (want["rewards"] + 1).sum()
+        )
 
     def test_backpressure(self):
         """Actors block on acquire when the consumer lags; no data is
