@@ -154,13 +154,23 @@ def _bias_relu_eligible(y: t.Tensor) -> bool:
     )
 
 
+def _bias_f32(bias: t.Tensor) -> t.Tensor:
+    """The bias as the kernels take it: fp32, contiguous and 16-byte
+    aligned. An fp32 parameter that is a view into a larger buffer (a
+    flat parameter buffer, a slice) comes through ``float()`` and
+    ``contiguous()`` as the same storage at the same offset, so a
+    misaligned one is copied."""
+    b = bias.detach().float().contiguous()
+    return b if b.data_ptr() % 16 == 0 else b.clone()
+
+
 class _BiasReLUFn(t.autograd.Function):
     """In place on a bias-free conv output: y = relu(y + bias)."""
 
     @staticmethod
     def forward(ctx, y: t.Tensor, bias: t.Tensor):
         ext = _require_ext()
-        ext.bias_relu_(_rows_view(y), bias.detach().float().contiguous())
+        ext.bias_relu_(_rows_view(y), _bias_f32(bias))
         ctx.mark_dirty(y)
         ctx.save_for_backward(y)
         ctx.bias_dtype = bias.dtype
@@ -190,7 +200,7 @@ class _BiasReLUFlatFn(t.autograd.Function):
         ext = _require_ext()
         N, C, H, W = y.shape
         out = ext.bias_relu_flat(
-            _rows_view(y), bias.detach().float().contiguous(), N
+            _rows_view(y), _bias_f32(bias), N
         )
         ctx.save_for_backward(out)
         ctx.shape = (N, C, H, W)
@@ -231,7 +241,10 @@ def bias_relu(y: t.Tensor, bias: t.Tensor,
         if y.shape[1] * y.shape[2] * y.shape[3] <= 32768:
             return _BiasReLUFlatFn.apply(y, bias)
         return _BiasReLUFn.apply(y, bias).flatten(1)
-    out = F.relu(y + bias.to(y.dtype).view(1, -1, 1, 1))
+    # threshold, not relu: ``s <= 0 ? +0 : s`` is the kernels' ReLU on
+    # every value (NaN kept, -0 -> +0); ATen's CPU relu returns -0 for
+    # -0. Its backward is relu's, threshold_backward.
+    out = F.threshold(y + bias.to(y.dtype).view(1, -1, 1, 1), 0.0, 0.0)
     return out.flatten(1) if flatten else out
 
 

@@ -11,9 +11,17 @@
 // - bias_relu_: ONE in-place pass, y = relu(bf16(float(y) +
 //   float(bf16(bias[c])))) — the exact rounding sequence of autocast's
 //   bf16 bias, ATen's fp32-opmath add_ and ReLU, so results are
-//   bit-identical to the unfused path.
+//   bit-identical to the unfused path. Checked on an MI355X for every
+//   bf16 value of y against biases that include ties, subnormals,
+//   +-inf and NaN (tests/test_bias_act_gpu.py): the ReLU is
+//   s <= 0 ? +0 : s, so a NaN sum stays NaN and every other
+//   non-positive sum, -0 included, gives +0, as ATen's relu does on
+//   the device (on the CPU it returns -0 for -0). Nothing is flushed:
+//   a subnormal bias, a subnormal fp32 sum and a subnormal bf16 result
+//   all come out as IEEE arithmetic gives them.
 // - bias_relu_bwd: ONE pass reads gy and the saved activation y,
-//   writes gx = y > 0 ? gy : 0 and accumulates the per-channel sum of
+//   writes gx = y <= 0 ? +0 : gy (threshold_backward: a NaN activation
+//   passes gy through) and accumulates the per-channel sum of
 //   gx. The sum is deterministic: fp32 per-thread partials over a fixed
 //   row assignment, a fixed-order LDS reduction per block, per-block
 //   partials in a small buffer and a fixed-order finishing kernel (no

@@ -1197,8 +1197,9 @@ void bias_relu_(Tensor y, Tensor bias) {
                    (int)y.size(1), current_stream());
 }
 
-// {gx = y > 0 ? gy : 0 as [R, C] bf16, per-channel sum of gx rounded to
-// bf16 and returned as fp32 [C]}; the sum is deterministic.
+// {gx = y <= 0 ? 0 : gy as [R, C] bf16 (NaN y passes gy), per-channel
+// sum of gx rounded to bf16 and returned as fp32 [C]}; the sum is
+// deterministic.
 std::vector<Tensor> bias_relu_bwd(Tensor gy, Tensor y) {
   check_rows_bf16(gy, "gy");
   check_rows_bf16(y, "y");
