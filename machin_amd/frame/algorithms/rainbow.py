@@ -27,6 +27,14 @@ independent noise for the online and the target net before the
 forwards, ``act_discrete_with_noise`` draws new noise for the online
 net and returns the argmax of every row (no epsilon, no host RNG read),
 and ``act_discrete`` runs with the noise switched off.
+
+``distribution="quantile"`` replaces the categorical head by quantile
+regression (QR-DQN): ``qnet(state) -> [batch, action_num, N]`` quantile
+values (a ``NoisyDuelingC51Head`` returns exactly that), trained with
+the quantile Huber loss of threshold ``huber_kappa`` through
+:func:`machin_amd.ops.quantile_huber_loss`. There is no support to
+choose: ``value_min`` / ``value_max`` are accepted and ignored. It
+implies ``fused_loss`` and excludes ``dist_from_logits``.
 """
 from typing import Any, Dict, List, Union
 
@@ -60,8 +68,23 @@ class RAINBOW(DQNPer):
         dist_from_logits: bool = False,
         exact_nstep_bootstrap: bool = False,
         noisy_nets: bool = False,
+        distribution: str = "categorical",
+        huber_kappa: float = 1.0,
         **kwargs,
     ):
+        if distribution not in ("categorical", "quantile"):
+            raise ValueError(
+                "distribution must be 'categorical' or 'quantile'."
+            )
+        if distribution == "quantile":
+            if dist_from_logits:
+                raise ValueError(
+                    "distribution='quantile' has no logits: "
+                    "dist_from_logits=True does not apply."
+                )
+            if not float(huber_kappa) >= 0.0:
+                raise ValueError("huber_kappa must be >= 0.")
+            fused_loss = True
         if dist_from_logits and not fused_loss:
             raise ValueError("dist_from_logits=True requires fused_loss=True.")
         if exact_nstep_bootstrap and not fused_loss:
@@ -85,6 +108,8 @@ class RAINBOW(DQNPer):
         self.dist_from_logits = bool(dist_from_logits)
         self.exact_nstep_bootstrap = bool(exact_nstep_bootstrap)
         self.noisy_nets = bool(noisy_nets)
+        self.distribution = distribution
+        self.huber_kappa = float(huber_kappa)
         if self.noisy_nets:
             for name, net in (("qnet", self.qnet),
                               ("qnet_target", self.qnet_target)):
@@ -102,12 +127,14 @@ class RAINBOW(DQNPer):
     # ------------------------------------------------------------------
     def _criticize(self, state: Dict[str, Any], use_target: bool = False,
                    **__):
-        """Returns the distribution [B, A, N]."""
+        """Returns the distribution (or the quantile values) [B, A, N]."""
         net = self.qnet_target if use_target else self.qnet
         return safe_return(safe_call(net, state))
 
     def _q_values(self, dist: t.Tensor) -> t.Tensor:
         B, A, N = dist.shape
+        if self.distribution == "quantile":
+            return dist.float().mean(dim=2)
         if self.dist_from_logits:
             dist = t.softmax(dist.float(), dim=2)
         support = t.linspace(
@@ -259,7 +286,19 @@ class RAINBOW(DQNPer):
         device = dist.device
         action_index = action["action"].to(device=device, dtype=t.long).view(B)
 
-        if self.fused_loss:
+        if self.distribution == "quantile":
+            # action selection, gather, Bellman target and the quantile
+            # Huber loss in one op (one kernel each way on ROCm)
+            with t.no_grad():
+                online_next = self._criticize(next_state)
+                target_next = self._criticize(next_state, use_target=True)
+            per_sample, _, _ = ops.quantile_huber_loss(
+                dist, action_index, online_next, target_next,
+                reward.to(device), terminal.to(device),
+                self._bootstrap_discount(others, device),
+                self.huber_kappa,
+            )
+        elif self.fused_loss:
             # action selection, gather, projection and cross entropy in
             # one op (one kernel each way on ROCm)
             with t.no_grad():
@@ -335,6 +374,8 @@ class RAINBOW(DQNPer):
         fc.setdefault("value_max", 10.0)
         fc.setdefault("reward_future_steps", 3)
         fc.setdefault("noisy_nets", False)
+        fc.setdefault("distribution", "categorical")
+        fc.setdefault("huber_kappa", 1.0)
         return config
 
     @classmethod

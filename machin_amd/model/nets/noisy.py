@@ -172,7 +172,9 @@ class NoisyDuelingC51Head(nn.Module):
     ``NoisyLinear -> ReLU -> NoisyLinear``, combined per atom into the
     LOGITS ``v + a - a.mean(dim=1, keepdim=True)`` ``[B, A, N]`` (fp32).
     Use it with ``RAINBOW(fused_loss=True, dist_from_logits=True,
-    noisy_nets=True)``."""
+    noisy_nets=True)``. The output is unnormalised, so the same head
+    serves ``RAINBOW(distribution="quantile")`` as is: read as dueling
+    quantile values, with ``atom_num`` the number of quantiles."""
 
     def __init__(self, feature_dim: int, action_num: int, atom_num: int,
                  hidden: int = 512, sigma0: float = 0.5):

@@ -681,6 +681,200 @@ def c51_loss(
 
 
 # ======================================================================
+# distributional RL: quantile regression (QR-DQN / IQN / FQF loss)
+# ======================================================================
+def _quantile_loss_check(theta, action, next_online, next_target, reward,
+                         terminal, discount, kappa, taus):
+    """Shared argument validation of :func:`quantile_huber_loss`;
+    returns ``(action [B], reward [B], terminal [B], discount float or
+    [B], kappa float, taus None or [B, N])``."""
+    if theta.dim() != 3:
+        raise ValueError("theta must be [B, A, N]")
+    B, A, N = theta.shape
+    if next_online.dim() != 3 or next_online.shape[:2] != (B, A):
+        raise ValueError("next_online must be [B, A, M]")
+    M = next_online.shape[2]
+    if next_target.shape != next_online.shape:
+        raise ValueError("next_target must have next_online's shape")
+    for name, x in (("next_online", next_online),
+                    ("next_target", next_target)):
+        if x.dtype != theta.dtype:
+            raise ValueError(f"{name} must have theta's dtype")
+    if not (1 <= N <= 256 and 1 <= M <= 256):
+        raise ValueError("quantiles must be in [1, 256]")
+    if not 1 <= A <= 64:
+        raise ValueError("actions must be in [1, 64]")
+    kappa = float(kappa)
+    if not kappa >= 0.0:
+        raise ValueError("kappa must be >= 0")
+    if action.dtype != t.int64 or action.numel() != B:
+        raise ValueError("action must be int64 [B] or [B, 1]")
+    if reward.numel() != B or terminal.numel() != B:
+        raise ValueError("reward and terminal must have B elements")
+    if t.is_tensor(discount):
+        if discount.dtype != t.float32 or discount.numel() != B:
+            raise ValueError("a tensor discount must be float32 [B]")
+        discount = discount.detach().reshape(B)
+    else:
+        discount = float(discount)
+    if taus is not None:
+        if not t.is_tensor(taus) or taus.dtype != t.float32 \
+                or taus.shape != (B, N):
+            raise ValueError("taus must be float32 [B, N]")
+        taus = taus.detach()
+    for name, x in (("action", action), ("next_online", next_online),
+                    ("next_target", next_target), ("reward", reward),
+                    ("terminal", terminal), ("discount", discount),
+                    ("taus", taus)):
+        if t.is_tensor(x) and x.device != theta.device:
+            raise ValueError(f"{name} must be on theta's device")
+    return (
+        action.reshape(B),
+        reward.detach().float().reshape(B),
+        terminal.detach().float().reshape(B),
+        discount, kappa, taus,
+    )
+
+
+def _quantile_huber_loss_torch(
+    theta: t.Tensor, action: t.Tensor, next_online: t.Tensor,
+    next_target: t.Tensor, reward: t.Tensor, terminal: t.Tensor,
+    discount, kappa: float = 1.0, taus: t.Tensor = None,
+):
+    """Torch composition of :func:`quantile_huber_loss` (the CPU path
+    and the reference the kernel is tested and timed against).
+    Differentiable with respect to ``theta``. Computes in fp32; float64
+    inputs are accepted here (not by the kernel) and computed in
+    float64, for gradient checks."""
+    if theta.dtype not in (t.float32, t.bfloat16, t.float64):
+        raise ValueError("theta must be float32 or bfloat16")
+    action, reward, terminal, discount, kappa, taus = _quantile_loss_check(
+        theta, action, next_online, next_target, reward, terminal,
+        discount, kappa, taus,
+    )
+    B, A, N = theta.shape
+    M = next_target.shape[2]
+    dev = theta.device
+    ct = t.float64 if theta.dtype == t.float64 else t.float32
+    rows = t.arange(B, device=dev)
+    with t.no_grad():
+        best = next_online.to(ct).sum(dim=2).argmax(dim=1)
+        if not t.is_tensor(discount):
+            discount = t.full((B,), discount, device=dev, dtype=ct)
+        gamma = discount.to(ct) * (1.0 - terminal.to(ct))
+        target = reward.to(ct).view(B, 1) \
+            + gamma.view(B, 1) * next_target[rows, best].to(ct)
+        if taus is None:
+            tau = (2 * t.arange(N, device=dev) + 1).to(ct) / (2 * N)
+            tau = tau.view(1, N, 1)
+        else:
+            tau = taus.to(ct).view(B, N, 1)
+    th = theta[rows, action.clamp(0, A - 1)].to(ct)
+    u = target.view(B, 1, M) - th.view(B, N, 1)
+    w = t.where(u < 0, 1.0 - tau, tau)
+    au = u.abs()
+    if kappa > 0:
+        huber = t.where(au <= kappa, u * u / (2.0 * kappa),
+                        au - 0.5 * kappa)
+    else:
+        huber = au
+    loss = (w * huber).sum(dim=(1, 2)) / M
+    return loss, target, best
+
+
+class _QuantileHuberLoss(t.autograd.Function):
+    @staticmethod
+    def forward(ctx, theta, action, next_online, next_target, reward,
+                terminal, discount, kappa, taus):
+        tensor_discount = t.is_tensor(discount)
+        loss, target, best, grad_row = _require_ext().quantile_loss_fwd(
+            theta.contiguous(), action, next_online.contiguous(),
+            next_target.contiguous(), reward, terminal,
+            discount.contiguous() if tensor_discount else None,
+            0.0 if tensor_discount else discount, kappa,
+            None if taus is None else taus.contiguous(),
+        )
+        ctx.save_for_backward(action, grad_row)
+        ctx.actions = theta.shape[1]
+        ctx.bf16 = theta.dtype == t.bfloat16
+        ctx.mark_non_differentiable(target, best)
+        return loss, target, best
+
+    @staticmethod
+    def backward(ctx, g_loss, g_target, g_best):
+        action, grad_row = ctx.saved_tensors
+        grad = _require_ext().quantile_loss_bwd(
+            action, grad_row, g_loss.contiguous().float(), ctx.actions,
+            ctx.bf16,
+        )
+        return (grad,) + (None,) * 8
+
+
+def quantile_huber_loss(
+    theta: t.Tensor, action: t.Tensor, next_online: t.Tensor,
+    next_target: t.Tensor, reward: t.Tensor, terminal: t.Tensor,
+    discount, kappa: float = 1.0, taus: t.Tensor = None,
+):
+    """Fused quantile-regression loss head (QR-DQN; with ``taus`` also
+    the loss of IQN and FQF) with double-DQN action selection and a
+    per-sample discount: returns ``(loss [B], target [B, M], best
+    [B])``.
+
+    ``theta`` is ``[B, A, N]`` (batch, actions, quantiles), the online
+    net on the sampled states; ``next_online`` and ``next_target`` are
+    ``[B, A, M]``, the online and the target net on the next states.
+    All three are fp32 or all three bf16. ``action`` is int64 ``[B]``
+    or ``[B, 1]``, ``reward`` and ``terminal`` hold ``B`` elements (cast
+    to fp32), ``discount`` is a float or an fp32 ``[B]`` tensor, e.g.
+    ``gamma ** m`` for n-step windows of ``m`` steps, ``kappa >= 0`` is
+    the Huber threshold (0: the plain quantile loss) and ``taus`` is
+    ``None`` for the midpoints ``tau_i = (2i + 1) / (2N)`` or an fp32
+    ``[B, N]`` tensor of fractions in ``[0, 1]``. Limits:
+    ``1 <= N, M <= 256``, ``1 <= A <= 64``.
+
+    All in fp32::
+
+        q[b, a]  = sum_j next_online[b, a, j]
+        best[b]  = lowest a with maximal q[b, a]
+        T[b, j]  = reward_b + discount_b (1 - terminal_b)
+                              next_target[b, best_b, j]
+        a_b      = clamp(action[b], 0, A - 1)
+        u_ij     = T[b, j] - theta[b, a_b, i]
+        w_ij     = 1 - tau_i if u_ij < 0 else tau_i
+        L(u)     = u^2 / (2 kappa) if |u| <= kappa else |u| - kappa / 2
+                   (kappa > 0), or |u| (kappa = 0)
+        loss[b]  = (1 / M) sum_i sum_j w_ij L(u_ij)
+
+    ``loss`` is differentiable with respect to ``theta`` only
+    (``-g_b (1 / M) sum_j w_ij D(u_ij)`` with ``D(u) = clamp(u, -kappa,
+    kappa) / kappa``, or ``sign(u)`` for ``kappa = 0``, in the taken
+    action's row and zero in the others); ``target`` (``T``) and
+    ``best`` (int64) are detached.
+
+    On ROCm this is one gfx950 kernel forward and one backward
+    (machin_amd/ops/hip/quantile_loss.hip) that never forms the
+    ``[B, N, M]`` intermediates; the CPU fallback is the same semantics
+    as a torch composition.
+    """
+    if not theta.is_cuda:
+        return _quantile_huber_loss_torch(
+            theta, action, next_online, next_target, reward, terminal,
+            discount, kappa, taus,
+        )
+    if theta.dtype not in (t.float32, t.bfloat16):
+        raise ValueError("theta must be float32 or bfloat16")
+    action, reward, terminal, discount, kappa, taus = _quantile_loss_check(
+        theta, action, next_online, next_target, reward, terminal,
+        discount, kappa, taus,
+    )
+    return _QuantileHuberLoss.apply(
+        theta, action.contiguous(), next_online.detach(),
+        next_target.detach(), reward.contiguous(), terminal.contiguous(),
+        discount, kappa, taus,
+    )
+
+
+# ======================================================================
 # NoisyLinear (factorised Gaussian noise) and its noise fill
 # ======================================================================
 # Largest batch (rows of x) the fused kernels take; above it the
@@ -1726,6 +1920,7 @@ __all__ = [
     "categorical_projection",
     "categorical_policy_head",
     "c51_loss",
+    "quantile_huber_loss",
     "noisy_linear",
     "factorised_noise_",
     "FusedPolyak",

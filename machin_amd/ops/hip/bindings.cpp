@@ -41,6 +41,13 @@ void c51_loss_fwd_launch(const void*, const int64_t*, const void*,
 void c51_loss_bwd_launch(const void*, const int64_t*, const float*,
                          const float*, const float*, const float*, void*,
                          int64_t, int, int, bool, bool, hipStream_t);
+void quantile_loss_fwd_launch(const void*, const int64_t*, const void*,
+                              const void*, const float*, const float*,
+                              const float*, float, const float*, float*,
+                              float*, int64_t*, float*, int64_t, int, int,
+                              int, double, bool, hipStream_t);
+void quantile_loss_bwd_launch(const int64_t*, const float*, const float*,
+                              void*, int64_t, int, int, bool, hipStream_t);
 void multi_tensor_polyak_launch(void*, const int64_t*, int64_t, int64_t,
                                 float, hipStream_t);
 void fused_rmsprop_launch(void*, const int64_t*, int64_t, int64_t,
@@ -543,6 +550,107 @@ Tensor c51_loss_bwd(Tensor dist, Tensor action, Tensor proj, Tensor lse,
                       grad.data_ptr(), B, (int)A, (int)N,
                       dist.scalar_type() == at::kBFloat16, from_logits,
                       current_stream());
+  return grad;
+}
+
+// ------------------------------------------------------------------
+// fused quantile-regression loss head
+// (semantics: machin_amd.ops.quantile_huber_loss)
+// ------------------------------------------------------------------
+void check_quantile_values(const Tensor& t, const Tensor& theta,
+                           const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 3, name,
+              " must be a contiguous [B, A, quantiles] CUDA tensor");
+  TORCH_CHECK(t.scalar_type() == theta.scalar_type() &&
+                  t.size(0) == theta.size(0) && t.size(1) == theta.size(1) &&
+                  t.device() == theta.device(),
+              name, " must match theta in dtype, batch, actions and device");
+}
+
+void check_quantile_matrix(const Tensor& t, const Tensor& theta,
+                           int64_t cols, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == theta.device() &&
+                  t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                  t.dim() == 2 && t.size(0) == theta.size(0) &&
+                  t.size(1) == cols,
+              name, " must be a contiguous [B, ", cols,
+              "] float32 tensor on theta's device");
+}
+
+// Returns {loss [B], target [B, M], best [B] int64, grad_row [B, N]}.
+// An undefined `discount` means the scalar one for every row, an
+// undefined `taus` the midpoints (2i + 1) / (2N).
+std::vector<Tensor> quantile_loss_fwd(Tensor theta, Tensor action,
+                                      Tensor next_online, Tensor next_target,
+                                      Tensor reward, Tensor terminal,
+                                      c10::optional<Tensor> discount,
+                                      double discount_scalar, double kappa,
+                                      c10::optional<Tensor> taus) {
+  TORCH_CHECK(theta.scalar_type() == at::kFloat ||
+                  theta.scalar_type() == at::kBFloat16,
+              "theta must be float32 or bfloat16");
+  check_quantile_values(theta, theta, "theta");
+  check_quantile_values(next_online, theta, "next_online");
+  check_quantile_values(next_target, theta, "next_target");
+  TORCH_CHECK(next_online.size(2) == next_target.size(2),
+              "next_online and next_target must have the same shape");
+  const int64_t B = theta.size(0), A = theta.size(1), N = theta.size(2);
+  const int64_t M = next_target.size(2);
+  TORCH_CHECK(N >= 1 && N <= 256 && M >= 1 && M <= 256,
+              "quantiles must be in [1, 256]");
+  TORCH_CHECK(A >= 1 && A <= 64, "actions must be in [1, 64]");
+  TORCH_CHECK(kappa >= 0.0, "kappa must be >= 0");  // false for a NaN
+  check_c51_rows(action, theta, at::kLong, "action");
+  check_c51_rows(reward, theta, at::kFloat, "reward");
+  check_c51_rows(terminal, theta, at::kFloat, "terminal");
+  const float* discount_ptr = nullptr;
+  if (discount.has_value() && discount->defined()) {
+    check_c51_rows(*discount, theta, at::kFloat, "discount");
+    discount_ptr = discount->data_ptr<float>();
+  }
+  const float* taus_ptr = nullptr;
+  if (taus.has_value() && taus->defined()) {
+    check_quantile_matrix(*taus, theta, N, "taus");
+    taus_ptr = taus->data_ptr<float>();
+  }
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(theta.device());
+  const auto f32 = theta.options().dtype(at::kFloat);
+  Tensor loss = at::empty({B}, f32);
+  Tensor target = at::empty({B, M}, f32);
+  Tensor best = at::empty({B}, theta.options().dtype(at::kLong));
+  Tensor grad_row = at::empty({B, N}, f32);
+  quantile_loss_fwd_launch(
+      theta.data_ptr(), action.data_ptr<int64_t>(), next_online.data_ptr(),
+      next_target.data_ptr(), reward.data_ptr<float>(),
+      terminal.data_ptr<float>(), discount_ptr, (float)discount_scalar,
+      taus_ptr, loss.data_ptr<float>(), target.data_ptr<float>(),
+      best.data_ptr<int64_t>(), grad_row.data_ptr<float>(), B, (int)A,
+      (int)N, (int)M, kappa, theta.scalar_type() == at::kBFloat16,
+      current_stream());
+  return {loss, target, best, grad_row};
+}
+
+// grad_theta [B, A, N], bfloat16 if `bf16` else float32, every element
+// written.
+Tensor quantile_loss_bwd(Tensor action, Tensor grad_row, Tensor g,
+                         int64_t A, bool bf16) {
+  TORCH_CHECK(grad_row.is_cuda() && grad_row.is_contiguous() &&
+                  grad_row.dim() == 2 &&
+                  grad_row.scalar_type() == at::kFloat,
+              "grad_row must be a contiguous [B, N] float32 CUDA tensor");
+  const int64_t B = grad_row.size(0), N = grad_row.size(1);
+  TORCH_CHECK(N >= 1 && N <= 256, "quantiles must be in [1, 256]");
+  TORCH_CHECK(A >= 1 && A <= 64, "actions must be in [1, 64]");
+  check_c51_rows(action, grad_row, at::kLong, "action");
+  check_c51_rows(g, grad_row, at::kFloat, "g");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(grad_row.device());
+  Tensor grad = at::empty(
+      {B, A, N},
+      grad_row.options().dtype(bf16 ? at::kBFloat16 : at::kFloat));
+  quantile_loss_bwd_launch(action.data_ptr<int64_t>(),
+                           grad_row.data_ptr<float>(), g.data_ptr<float>(),
+                           grad.data_ptr(), B, (int)A, (int)N, bf16,
+                           current_stream());
   return grad;
 }
 
@@ -1331,6 +1439,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("categorical_projection", &categorical_projection);
   m.def("c51_loss_fwd", &c51_loss_fwd);
   m.def("c51_loss_bwd", &c51_loss_bwd);
+  m.def("quantile_loss_fwd", &quantile_loss_fwd);
+  m.def("quantile_loss_bwd", &quantile_loss_bwd);
   m.def("noisy_linear_fwd", &noisy_linear_fwd);
   m.def("noisy_linear_bwd_input", &noisy_linear_bwd_input);
   m.def("noisy_linear_bwd_weight", &noisy_linear_bwd_weight);

@@ -25,6 +25,7 @@ SOURCES = [
     "scans.hip",
     "projection.hip",
     "c51_loss.hip",
+    "quantile_loss.hip",
     "noisy_linear.hip",
     "multi_tensor.hip",
     "distributions.hip",
@@ -35,6 +36,14 @@ SOURCES = [
     "conv1_wrw.hip",
     "bias_act.hip",
 ]
+# Per-source flags. quantile_loss.hip is scalar fp32 VALU code whose sums
+# have a fixed order; it is compiled without the packed fp32 instructions
+# (v_pk_*_f32) so that the compiler does not pair its pair-loop math.
+EXTRA_FLAGS = {
+    "quantile_loss.hip": [
+        "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+    ],
+}
 
 
 def _hipcc() -> str:
@@ -105,7 +114,7 @@ class BuildHipExt(Command):
             # compiles it as plain C++ against the HIP runtime headers
             cmd = (
                 [hipcc, "-c", src, "-o", obj]
-                + cflags + defines
+                + cflags + EXTRA_FLAGS.get(src_name, []) + defines
                 + [f"-I{p}" for p in includes]
             )
             print(" ".join(cmd), flush=True)
