@@ -777,7 +777,10 @@ def _quantile_huber_loss_torch(
         huber = t.where(au <= kappa, u * u / (2.0 * kappa),
                         au - 0.5 * kappa)
     else:
-        huber = au
+        # abs' backward is sign(u), which is 0 for a NaN: take a NaN
+        # through a product, so that the gradient keeps it as the
+        # kernel's does
+        huber = t.where(u.isnan(), u * u, au)
     loss = (w * huber).sum(dim=(1, 2)) / M
     return loss, target, best
 
@@ -835,7 +838,9 @@ def quantile_huber_loss(
     All in fp32::
 
         q[b, a]  = sum_j next_online[b, a, j]
-        best[b]  = lowest a with maximal q[b, a]
+        best[b]  = lowest a with maximal q[b, a]; a NaN q[b, a] counts
+                   as maximal: the lowest a with a NaN sum if there is
+                   one, as argmax has it
         T[b, j]  = reward_b + discount_b (1 - terminal_b)
                               next_target[b, best_b, j]
         a_b      = clamp(action[b], 0, A - 1)

@@ -63,6 +63,15 @@ __device__ __forceinline__ float ql_wave_sum(float v) {
   return v;
 }
 
+// r + g z with the product and the sum rounded separately. The
+// __fmul_rn and __fadd_rn forms are plain operators to this compiler and
+// contract to one fma, so contraction is switched off for the statement.
+__device__ __forceinline__ float ql_target(float r, float g, float z) {
+#pragma clang fp contract(off)
+  const float p = g * z;
+  return r + p;
+}
+
 // One pair: adds w L(u) to acc_l and w D(u) to acc_d, both still scaled
 // by kappa when HUBER (the caller divides once per lane):
 //   kappa L(u) = c (|u| - c / 2),  kappa D(u) = clamp(u, -kappa, kappa)
@@ -139,11 +148,12 @@ __global__ void __launch_bounds__(QL_MAX_QUANTILES)
 
     int best = 0;
     if (active) {
-      // ascending a, strict >: ties go to the lowest index
+      // ascending a, strict >: ties go to the lowest index. A NaN sum
+      // counts as maximal, as argmax has it: the first one is kept
       float best_q = -INFINITY;
       for (int a = 0; a < A; ++a) {
         float q = q_s[a];
-        if (q > best_q) {
+        if (best_q == best_q && (q > best_q || q != q)) {
           best_q = q;
           best = a;
         }
@@ -159,7 +169,7 @@ __global__ void __launch_bounds__(QL_MAX_QUANTILES)
       const float g =
           (discount ? discount[b] : discount_scalar) * (1.0f - terminal[b]);
       for (int j = tid; j < M; j += nthreads) {
-        float tj = __fadd_rn(r, __fmul_rn(g, ql_ld(row, j)));
+        float tj = ql_target(r, g, ql_ld(row, j));
         t_s[j] = tj;
         target[b * M + j] = tj;
       }

@@ -1,7 +1,10 @@
 """CPU tests of ``ops.quantile_huber_loss``: the fp32 torch fallback
 against the float64 reference under the derived bound ``(M + 16) 2^-24
 S`` (``util_quantile_loss.reference64``), argument validation and the
-``RAINBOW(distribution="quantile")`` option.
+``RAINBOW(distribution="quantile")`` option. The general-input,
+call-style and non-finite checks of ``util_quantile_loss`` run here on
+the fallback, which pins it to the kernel's contract and checks the
+references and the ``(M + 20) 2^-24 S`` bound without a device.
 """
 import numpy as np
 import pytest
@@ -10,7 +13,11 @@ import torch as t
 from machin_amd import ops
 from machin_amd.frame.algorithms import RAINBOW
 from util_quantile_loss import (
-    PixelQuantileNet, all_cases, make_case, reference64, run_op,
+    CONTAINMENT_SHAPE, GENERAL_MULTI_TRIP_SHAPE, NON_FINITE,
+    PixelQuantileNet, all_cases, check_bf16_gradient_overflow,
+    check_nonfinite_online, check_permutation, check_poisoned_sample,
+    check_reductions, check_scalar_discount, check_views, general_cases,
+    general_reference64, make_case, make_general_case, reference64, run_op,
     seeded_quantile_update, within_bound,
 )
 
@@ -22,6 +29,88 @@ def test_fallback_within_the_bound(shape, tie, kappa, given_taus, dtype):
     result = run_op(ops.quantile_huber_loss, case, kappa)
     assert not tie or t.equal(result[2], case.want_best)
     assert within_bound(case, result, ref, bound, "fallback")
+
+
+@general_cases
+def test_fallback_within_the_bound_on_general_inputs(
+        shape, kappa, scale, given_taus, dtype):
+    """``target`` bit-equal to the fp32 definition, loss and gradient
+    within ``(M + 20) 2^-24 S`` of float64 (``general_reference``)."""
+    case = make_general_case(shape, given_taus, dtype, scale)
+    ref, bound = general_reference64(shape, given_taus, dtype, scale, kappa)
+    result = run_op(ops.quantile_huber_loss, case, kappa)
+    assert within_bound(case, result, ref, bound, "fallback")
+
+
+@pytest.mark.parametrize("dtype", [t.float32, t.bfloat16], ids=str)
+@pytest.mark.parametrize("kappa", [1.0, 0.0])
+def test_fallback_multi_trip_shape(kappa, dtype):
+    case = make_general_case(GENERAL_MULTI_TRIP_SHAPE, True, dtype)
+    B, A = case.shape[:2]
+    # what blocks 0 to 2 read in their second trip is not what they read
+    # in the first (terminal is 0, 0, 1 after 0, 1, 0)
+    assert bool((case.discount[2048:] != case.discount[:3]).all())
+    assert bool((case.terminal[2048:] != case.terminal[:3]).any())
+    assert bool((case.action[2048:] != case.action[:3].clamp(0, A - 1)).all())
+    ref, bound = general_reference64(
+        GENERAL_MULTI_TRIP_SHAPE, True, dtype, 1.0, kappa)
+    result = run_op(ops.quantile_huber_loss, case, kappa)
+    assert within_bound(case, result, ref, bound, "fallback multi-trip")
+
+
+@pytest.mark.parametrize("dtype", [t.float32, t.bfloat16], ids=str)
+@pytest.mark.parametrize("given_taus", [False, True])
+@pytest.mark.parametrize("kappa", [1.0, 0.0])
+def test_fallback_follows_a_permutation_of_the_samples(
+        kappa, given_taus, dtype):
+    case = make_general_case((7, 3, 65, 33), given_taus, dtype)
+    check_permutation(ops.quantile_huber_loss, "cpu", case, kappa)
+
+
+@pytest.mark.parametrize("shape,dtype", [
+    ((5, 2, 6, 7), t.float32), ((5, 2, 6, 7), t.bfloat16),
+    (GENERAL_MULTI_TRIP_SHAPE, t.bfloat16)], ids=str)
+@pytest.mark.parametrize("kappa", [0.1, 0.0])
+def test_fallback_scalar_discount(shape, dtype, kappa):
+    case = make_general_case(shape, True, dtype)
+    check_scalar_discount(ops.quantile_huber_loss, "cpu", case, kappa)
+
+
+@pytest.mark.parametrize("dtype", [t.float32, t.bfloat16], ids=str)
+def test_fallback_as_it_is_called(dtype):
+    case = make_general_case((7, 3, 65, 33), True, dtype)
+    check_reductions(ops.quantile_huber_loss, "cpu", case, 1.0)
+    check_views(ops.quantile_huber_loss, "cpu", case, 1.0)
+
+
+@pytest.mark.parametrize("dtype", [t.float32, t.bfloat16], ids=str)
+@pytest.mark.parametrize("kappa", [1.0, 0.0])
+def test_fallback_best_with_non_finite_row_sums(kappa, dtype):
+    case = make_general_case((7, 3, 65, 33), False, dtype)
+    check_nonfinite_online(ops.quantile_huber_loss, "cpu", case, kappa)
+
+
+@pytest.mark.parametrize("dtype", [t.float32, t.bfloat16], ids=str)
+@pytest.mark.parametrize("kappa", [1.0, 0.0])
+@pytest.mark.parametrize("what,b", NON_FINITE)
+def test_fallback_non_finite_sample(what, b, kappa, dtype):
+    """For ``theta = +-inf`` the fallback's autograd gives NaN through
+    ``where`` (the kernel follows the definition and stays finite), so
+    its gradient is not asserted there."""
+    case = make_general_case((7, 3, 65, 33), True, dtype)
+    check_poisoned_sample(ops.quantile_huber_loss, "cpu", case, kappa, what,
+                          b, check_grad=not what.startswith("theta_"))
+
+
+@pytest.mark.parametrize("b", [1, 2049])
+def test_fallback_contains_a_nan_in_a_second_trip(b):
+    case = make_general_case(CONTAINMENT_SHAPE, False, t.bfloat16)
+    check_poisoned_sample(ops.quantile_huber_loss, "cpu", case, 1.0,
+                          "online_and_reward", b)
+
+
+def test_fallback_bf16_gradient_overflows_to_infinity():
+    check_bf16_gradient_overflow(ops.quantile_huber_loss, "cpu")
 
 
 @pytest.mark.parametrize("A,N,M,kappa,dtype", [

@@ -3,7 +3,29 @@ tests. Inputs lie on a dyadic grid (multiples of 1/8 in [-8, 8],
 ``discount`` 0.5, ``terminal`` 0 or 1), so every ``u_ij`` and every row
 sum is exact in fp32 and float64 alike: no indicator, Huber branch or
 ``best`` can flip between precisions. Cached results are shared: do not
-modify them."""
+modify them.
+
+General inputs (``make_general_case``, ``general_reference``) leave the
+grid: normal values at three scales, a per-sample ``discount`` and any
+``kappa``. Then ``T_j`` and ``u_ij`` round. ``target`` is compared bit
+for bit with ``T_hat``, the correctly rounded fp32 definition, computed
+operation by operation in float64 (a product of two fp32 numbers is
+exact there, and for a sum 53 >= 2 * 24 + 2 bits make the second
+rounding harmless). Loss and gradient are formed in float64 from
+``T_hat`` with ``u = T_hat_j - theta_i`` exact; ``fl(a - b)`` has the
+sign of ``a - b`` and the kernel's ``min(|u|, kappa)`` and clamp are
+continuous, so no indicator, Huber branch or sign differs between the
+two and no pair is left out. The bound keeps the magnitude sums of the
+dyadic one with the unit ``(M + 20) 2^-24``. Count for the loss: the
+``M + 14`` of the dyadic case (1 for ``w``, 2 for ``c (|u| - c / 2)``,
+``M`` multiply-adds, 2 for the factor and its product, 6 butterfly
+steps, 3 additions over the waves), 2 for the rounding of ``u``
+(``L(u (1 + e))`` moves by ``|u D(u)| e <= 2 L(u) e`` in both Huber
+regimes) and 1 for a ``kappa`` that fp32 cannot hold (it enters as
+``kappa_32 / kappa`` in the linear regime only): ``M + 17``. Gradient:
+``M + 4``, 1 for ``u`` (the clamp passes its error on at most once) and
+1 for ``kappa``: ``M + 6``. bf16 gradients add ``2^-8 |ref|`` as
+before."""
 import functools
 import random
 from types import SimpleNamespace
@@ -72,7 +94,8 @@ def op_args(case, kappa, device="cpu"):
         case.theta.to(device), case.action.to(device),
         case.next_online.to(device), case.next_target.to(device),
         case.reward.to(device), case.terminal.to(device),
-        case.discount.to(device), kappa,
+        case.discount.to(device) if t.is_tensor(case.discount)
+        else case.discount, kappa,
         None if case.taus is None else case.taus.to(device),
     )
 
@@ -91,13 +114,22 @@ def reference64(shape, given_taus, dtype, kappa, tie=False):
     gamma = case.discount.double() * (1.0 - case.terminal.double())
     target = case.reward.double().view(B, 1) \
         + gamma.view(B, 1) * case.next_target.double()[rows, best]
+    return _loss_and_gradient64(case, best, target, target, kappa, M + 16)
+
+
+def _loss_and_gradient64(case, best, target, u_target, kappa, roundings):
+    """``(ref, bound)`` of the loss and the taken row's gradient in
+    float64 for the float64 targets ``u_target``; ``target`` is what
+    ``ref.target`` reports."""
+    B, A, N, M = case.shape
+    rows = t.arange(B)
     if case.taus is None:
         tau = (2.0 * t.arange(N, dtype=t.float64) + 1.0) / (2.0 * N)
         tau = tau.view(1, N, 1).expand(B, N, 1)
     else:
         tau = case.taus.double().view(B, N, 1)
     th = case.theta.double()[rows, case.action.clamp(0, A - 1)]
-    u = target.view(B, 1, M) - th.view(B, N, 1)
+    u = u_target.view(B, 1, M) - th.view(B, N, 1)
     neg = (u < 0).double()
     w = neg * (1.0 - tau) + (1.0 - neg) * tau
     mag = tau + neg
@@ -106,18 +138,18 @@ def reference64(shape, given_taus, dtype, kappa, tie=False):
                     u.abs() - kappa / 2.0)
         D = u.clamp(-kappa, kappa) / kappa
     else:
-        L, D = u.abs(), t.sign(u)
+        L, D = u.abs(), t.where(u.isnan(), u, t.sign(u))  # sign(NaN) is 0
     g = case.g.double().view(B, 1)
     ref = SimpleNamespace(
         loss=(w * L).sum(dim=(1, 2)) / M, target=target, best=best,
         grad=-g * (w * D).sum(dim=2) / M,
     )
-    unit = (M + 16) * 2.0 ** -24
+    unit = roundings * 2.0 ** -24
     bound = SimpleNamespace(
         loss=unit * (mag * L).sum(dim=(1, 2)) / M,
         grad=unit * g.abs() * (mag * D.abs()).sum(dim=2) / M,
     )
-    if dtype == t.bfloat16:
+    if case.dtype == t.bfloat16:
         bound.grad = bound.grad + 2.0 ** -8 * ref.grad.abs()
     return ref, bound
 
@@ -131,9 +163,24 @@ def run_op(fn, case, kappa, device="cpu"):
     return loss.detach(), target, best, grad
 
 
-def within_bound(case, result, ref, bound, what):
+def same_bits(a, b):
+    """Equal bit for bit, except that any NaN equals any NaN."""
+    a, b = a.detach().cpu(), b.detach().cpu()
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return False
+    if not a.is_floating_point():
+        return t.equal(a, b)
+    ints = {2: t.int16, 4: t.int32, 8: t.int64}[a.element_size()]
+    nan = a.isnan()
+    return t.equal(nan, b.isnan()) \
+        and t.equal(a.view(ints)[~nan], b.view(ints)[~nan])
+
+
+def within_bound(case, result, ref, bound, what, check_grad=True):
     """``loss`` and the taken gradient row within the bound; ``best``,
-    ``target`` and untaken rows exact. Prints each worst error/bound."""
+    ``target`` and untaken rows exact. A NaN of the reference must be a
+    NaN of the result and the reverse, and an infinite reference value
+    must be met exactly. Prints each worst error/bound."""
     loss, target, best, grad = (x.detach().cpu() for x in result)
     B, A, N, M = case.shape
     assert loss.dtype == target.dtype == t.float32 and best.dtype == t.int64
@@ -141,15 +188,344 @@ def within_bound(case, result, ref, bound, what):
     a_b = case.action.clamp(0, A - 1)
     taken = t.zeros(B, A, dtype=t.bool)
     taken[t.arange(B), a_b] = True
-    ok = t.equal(best, ref.best) and t.equal(target.double(), ref.target) \
+    if ref.target.dtype == t.float32:  # the fp32 definition, bit for bit
+        exact = same_bits(target, ref.target)
+    else:
+        exact = t.equal(target.double(), ref.target)
+    ok = t.equal(best, ref.best) and exact \
         and bool((grad[~taken] == 0).all())
-    for name, got in (("loss", loss), ("grad", grad[t.arange(B), a_b])):
-        err = (got.double() - getattr(ref, name)).abs()
+    checked = (("loss", loss), ("grad", grad[t.arange(B), a_b]))
+    for name, got in checked[:1 + check_grad]:
+        got, want = got.double(), getattr(ref, name)
+        err = (got - want).abs()
         limit = getattr(bound, name)
-        ratio = float((err / limit.clamp_min(1e-300)).max())
+        nan = want.isnan()
+        good = (got == want) | (err <= limit)
+        finite = err.isfinite() & limit.isfinite()
+        ratio = float((err / limit.clamp_min(1e-300))[finite].max()) \
+            if bool(finite.any()) else 0.0
         print(f"{what} {name} worst error/bound {ratio:.3g}")
-        ok = ok and bool((err <= limit).all())
+        ok = ok and t.equal(got.isnan(), nan) and bool(good[~nan].all())
     return ok
+
+
+# ----------------------------------------------------------------------
+# general inputs
+# ----------------------------------------------------------------------
+# (B, A, N, M): two waves, tail 1 after the float4 loop; tail 3; tail 2
+# with M < 4; four waves, more actions than waves, tail 2; both limits,
+# tail 3
+GENERAL_SHAPES = [(7, 3, 65, 33), (5, 2, 6, 7), (6, 3, 3, 2),
+                  (4, 5, 200, 130), (3, 64, 256, 255)]
+# 0.1 is no fp32 number; 1024 at scale 1e-3 makes every pair quadratic,
+# 2^-10 at scale 1e3 every pair linear
+GENERAL_KAPPAS = [1.0, 0.25, 0.0, 0.1, 1024.0, 2.0 ** -10]
+SCALES = [1.0, 1e-3, 1e3]
+# second trips of the grid with two waves and three actions; with the
+# poisoned sample of the containment test
+GENERAL_MULTI_TRIP_SHAPE = (2051, 3, 65, 6)
+CONTAINMENT_SHAPE = (2051, 2, 65, 5)
+NAN, INF = float("nan"), float("inf")
+# (what, sample) of ``poisoned`` on (7, 3, 65, 33): sample 4 is terminal,
+# the others are not, and none holds a given tau of 0 or 1 (0 * inf)
+NON_FINITE = [("reward", 2), ("discount", 2), ("next_target", 2),
+              ("terminal_inf", 4), ("theta", 2), ("theta_pinf", 2),
+              ("theta_ninf", 5)]
+
+
+def general_cases(test):
+    """Shapes x kappa x scale x fractions x dtype, the full product."""
+    for name, values in (("dtype", [t.float32, t.bfloat16]),
+                         ("given_taus", [False, True]), ("scale", SCALES),
+                         ("kappa", GENERAL_KAPPAS),
+                         ("shape", GENERAL_SHAPES)):
+        test = pytest.mark.parametrize(name, values, ids=str)(test)
+    return test
+
+
+def best_by_rule(next_online):
+    """A NaN row sum counts as maximal: the lowest index among NaN rows,
+    else the lowest index of the maximum. Written without argmax."""
+    q = next_online.double().sum(dim=2)
+    A = q.shape[1]
+    nan = q.isnan()
+    top = q.masked_fill(nan, -INF).max(dim=1, keepdim=True).values
+    candidate = t.where(nan.any(dim=1, keepdim=True), nan, q == top)
+    return t.where(candidate, t.arange(A), A).min(dim=1).values
+
+
+def discount_of(case):
+    B = case.shape[0]
+    if t.is_tensor(case.discount):
+        return case.discount
+    return t.full((B,), case.discount)  # rounds the float to fp32
+
+
+def target_fp32(case, best):
+    """``T_hat = fl(r + fl(fl(d (1 - term)) z))``: each operation in
+    float64 on fp32 values, rounded to fp32."""
+    B = case.shape[0]
+    gamma = (discount_of(case).double()
+             * (1.0 - case.terminal.double())).float().double()
+    z = case.next_target[t.arange(B), best].double()
+    product = (gamma.view(B, 1) * z).float().double()
+    return (case.reward.double().view(B, 1) + product).float()
+
+
+@functools.lru_cache(maxsize=None)
+def make_general_case(shape, given_taus=False, dtype=t.float32, scale=1.0):
+    """Normal inputs of one scale on the CPU, a discount that differs
+    between neighbouring samples and between trips of the grid, and
+    planted exact zeros of ``u``: ``theta[b, a_b, 0] = T_hat[b, 0]`` for
+    every sample (fp32) or every terminal one, whose reward is rounded
+    to bf16 for it (bf16)."""
+    B, A, N, M = shape
+    gen = t.Generator().manual_seed(B * 100003 + A * 1009 + N * 31 + M + 7)
+
+    def normal(*size):
+        return t.randn(size, generator=gen) * scale
+
+    perm = t.stack([t.randperm(A, generator=gen) for _ in range(B)])
+    case = SimpleNamespace(
+        shape=shape, dtype=dtype, theta=normal(B, A, N).to(dtype),
+        next_online=(normal(B, A, M)
+                     + 4.0 * scale * perm.view(B, A, 1)).to(dtype),
+        next_target=normal(B, A, M).to(dtype),
+        action=t.randint(-2, A + 2, (B,), generator=gen),  # clamped
+        reward=normal(B), terminal=(t.arange(B) % 3 == 1).float(),
+        discount=t.full((B,), 0.99).pow((1 + t.arange(B) % 3).float()),
+        g=t.randn(B, generator=gen), taus=None,
+    )
+    if given_taus:
+        case.taus = t.rand(B, N, generator=gen)
+        case.taus[0, 0], case.taus[B - 1, N - 1] = 0.0, 1.0
+    if B > 2048:  # the second trip takes other actions than the first
+        case.action[2048:] = (case.action[:B - 2048].clamp(0, A - 1) + 1) % A
+    # fp32 summation order cannot decide the argmax
+    x = case.next_online.double()
+    top = x.sum(dim=2).topk(2, dim=1)
+    magnitude = x.abs().sum(dim=2).gather(1, top.indices).sum(dim=1)
+    gap = top.values[:, 0] - top.values[:, 1]
+    assert bool((gap > 2 * (M + 6) * 2.0 ** -24 * magnitude).all())
+    rows = t.arange(B)
+    if dtype == t.bfloat16:
+        rows = rows[case.terminal > 0]
+        case.reward[rows] = case.reward[rows].bfloat16().float()
+    a_b = case.action.clamp(0, A - 1)[rows]
+    t_hat = target_fp32(case, best_by_rule(case.next_online))
+    case.theta[rows, a_b, 0] = t_hat[rows, 0].to(dtype)
+    assert t.equal(case.theta[rows, a_b, 0].float(), t_hat[rows, 0])
+    return case
+
+
+def clone_case(case, **changes):
+    """A copy that may be modified."""
+    fields = {k: v.clone() if t.is_tensor(v) else v
+              for k, v in vars(case).items()}
+    fields.update(changes)
+    return SimpleNamespace(**fields)
+
+
+def general_reference(case, kappa):
+    """``(ref, bound)`` of any case by the module docstring's recipe;
+    ``ref.target`` is the fp32 ``T_hat``. NaNs and infinities follow the
+    definitions."""
+    best = best_by_rule(case.next_online)
+    t_hat = target_fp32(case, best)
+    return _loss_and_gradient64(
+        case, best, t_hat, t_hat.double(), kappa, case.shape[3] + 20)
+
+
+@functools.lru_cache(maxsize=None)
+def general_reference64(shape, given_taus, dtype, scale, kappa):
+    return general_reference(
+        make_general_case(shape, given_taus, dtype, scale), kappa)
+
+
+def permuted(case, perm):
+    """The same samples in another order."""
+    return SimpleNamespace(**{
+        k: v[perm].clone() if t.is_tensor(v) else v
+        for k, v in vars(case).items()})
+
+
+def poisoned(case, what, b):
+    """A copy with one non-finite value in sample ``b``: in the last
+    element of the row that the sample reads, which is the tail of the
+    pair loop and the last wave."""
+    case = clone_case(case)
+    B, A, N, M = case.shape
+    a_b = int(case.action[b].clamp(0, A - 1))
+    best = int(best_by_rule(case.next_online)[b])
+    if what == "reward":
+        case.reward[b] = NAN
+    elif what == "discount":
+        case.discount[b] = NAN
+    elif what == "next_target":
+        case.next_target[b, best, M - 1] = NAN
+    elif what == "terminal_inf":  # 0 * inf
+        assert case.terminal[b] == 1
+        case.next_target[b, best, M - 1] = INF
+    elif what == "theta":
+        case.theta[b, a_b, N - 1] = NAN
+    elif what == "theta_pinf":
+        case.theta[b, a_b, N - 1] = INF
+    elif what == "theta_ninf":
+        case.theta[b, a_b, N - 1] = -INF
+    elif what == "online_and_reward":  # q_s, t_s and part_s all get one
+        case.next_online[b, A - 1, 0] = NAN
+        case.reward[b] = NAN
+    else:
+        raise ValueError(what)
+    return case
+
+
+def contained(clean, dirty, touched):
+    """Every sample outside ``touched`` has the bits of the clean run."""
+    keep = t.ones(clean[0].shape[0], dtype=t.bool)
+    keep[list(touched)] = False
+    return all(same_bits(a.detach().cpu()[keep], b.detach().cpu()[keep])
+               for a, b in zip(clean, dirty))
+
+
+# The checks below run on the CPU fallback and on the device alike:
+# ``fn`` is ``ops.quantile_huber_loss``.
+def check_permutation(fn, device, case, kappa):
+    """Every per-sample input is read at its own sample's index."""
+    B = case.shape[0]
+    perm = t.randperm(B, generator=t.Generator().manual_seed(3))
+    assert not t.equal(perm, t.arange(B))
+    straight = run_op(fn, case, kappa, device)
+    shuffled = run_op(fn, permuted(case, perm), kappa, device)
+    for a, b in zip(straight, shuffled):
+        assert same_bits(a.cpu()[perm], b)
+
+
+def check_scalar_discount(fn, device, case, kappa, discount=0.97):
+    B = case.shape[0]
+    scalar = clone_case(case, discount=discount)
+    tensor = clone_case(case, discount=t.full((B,), discount))
+    ref, bound = general_reference(tensor, kappa)
+    result = run_op(fn, scalar, kappa, device)
+    for a, b in zip(result, run_op(fn, tensor, kappa, device)):
+        assert same_bits(a, b)
+    assert within_bound(scalar, result, ref, bound, f"scalar B={B}")
+
+
+def check_reductions(fn, device, case, kappa):
+    """``mean()`` and a weighted sum hand the backward an expanded or a
+    computed ``g``; both must equal the explicit contiguous one."""
+    B = case.shape[0]
+    weights = t.rand(B, generator=t.Generator().manual_seed(5)).to(device)
+    for reduce, g in ((lambda loss: loss.mean(), t.full((B,), 1.0 / B)),
+                      (lambda loss: (loss * weights).sum(), weights)):
+        args = list(op_args(case, kappa, device))
+        args[0] = args[0].clone().requires_grad_(True)
+        reduce(fn(*args)[0]).backward()
+        explicit = run_op(fn, clone_case(case, g=g.cpu()), kappa, device)
+        assert args[0].grad.abs().sum() > 0
+        assert same_bits(args[0].grad, explicit[3])
+
+
+def check_views(fn, device, case, kappa):
+    """Every second element of a wider tensor as ``theta`` and as the
+    next-state values: the bits of contiguous clones, and the gradient
+    in the view's base with zeros between."""
+    args = list(op_args(case, kappa, device))
+    wide = []
+    for i in (0, 2, 3):
+        B, A, K = args[i].shape
+        # the gaps hold a value that would show if it were read
+        base = t.full((B, A, 2 * K), 77.0, dtype=case.dtype, device=device)
+        base[:, :, ::2] = args[i]
+        wide.append(base)
+        args[i] = base[:, :, ::2]
+    wide[0].requires_grad_(True)
+    args[0] = wide[0][:, :, ::2]
+    assert not any(args[i].is_contiguous() for i in (0, 2, 3))
+    loss, target, best = fn(*args)
+    loss.backward(case.g.to(device))
+    want = run_op(fn, case, kappa, device)
+    for a, b in zip((loss, target, best, wide[0].grad[:, :, ::2]), want):
+        assert same_bits(a, b)
+    assert bool((wide[0].grad[:, :, 1::2] == 0).all())
+
+
+def check_nonfinite_online(fn, device, case, kappa):
+    """NaN and infinite row sums of ``next_online``: ``best`` by the
+    rule, everything else by the definitions for that ``best``."""
+    B, A, N, M = case.shape
+    assert B >= 7 and A >= 3
+    dirty = clone_case(case)
+    x = dirty.next_online
+    first = best_by_rule(x)
+    other = [int((first[b] + 1) % A) for b in range(B)]
+    x[0, other[0], M - 1] = NAN                    # one row
+    x[1, 1, 0] = x[1, 2, 3] = NAN                  # two rows
+    x[2, :, 1] = NAN                               # all rows
+    x[3, other[3], 2] = INF                        # a +inf row
+    x[4, other[4], 0], x[4, other[4], 1] = INF, -INF   # inf - inf
+    x[5, 0, 0], x[5, 1, 0], x[5, 2, 0] = INF, NAN, INF  # NaN above +inf
+    want_best = [other[0], 1, 0, other[3], other[4], 1, int(first[6])]
+    ref, bound = general_reference(dirty, kappa)
+    assert ref.best[:7].tolist() == want_best
+    result = run_op(fn, dirty, kappa, device)
+    assert result[2].cpu()[:7].tolist() == want_best
+    assert within_bound(dirty, result, ref, bound, "non-finite online")
+    assert contained(run_op(fn, case, kappa, device), result, range(6))
+    return result
+
+
+def check_poisoned_sample(fn, device, case, kappa, what, b,
+                          check_grad=True):
+    """One non-finite value in sample ``b``: that sample by the
+    definitions, every other sample as without it."""
+    B, A, N, M = case.shape
+    dirty = poisoned(case, what, b)
+    ref, bound = general_reference(dirty, kappa)
+    result = run_op(fn, dirty, kappa, device)
+    assert within_bound(dirty, result, ref, bound, what, check_grad)
+    assert contained(run_op(fn, case, kappa, device), result, [b])
+    loss, target, best, grad = (x.cpu() for x in result)
+    row = grad[b, int(case.action[b].clamp(0, A - 1))].float()
+    if what in ("theta_pinf", "theta_ninf"):
+        assert loss[b] == INF
+        if check_grad:  # finite: -/+ w times the scale
+            assert bool(row.isfinite().all()) and row[N - 1] != 0
+            assert bool(row[N - 1] > 0) == ((what == "theta_pinf")
+                                            == bool(case.g[b] > 0))
+    elif what == "theta":
+        assert bool(loss[b].isnan()) and bool(row[N - 1].isnan())
+        assert bool(row[:N - 1].isfinite().all())
+    else:
+        assert bool(loss[b].isnan()) and bool(row.isnan().all())
+        if what in ("next_target", "terminal_inf"):
+            assert bool(target[b, M - 1].isnan())
+            assert bool(target[b, :M - 1].isfinite().all())
+        else:
+            assert bool(target[b].isnan().all())
+    return result
+
+
+def check_bf16_gradient_overflow(fn, device):
+    """A gradient that fp32 holds and bf16 does not stores as an
+    infinity, never as a NaN: ``kappa = 0``, every ``u > 0``, ``tau =
+    1`` and ``M = 2`` make the row's sum exactly -1, times ``g_b =
+    3.4e38`` (above bf16's largest number plus half a step)."""
+    case = clone_case(make_general_case((6, 3, 3, 2), True, t.bfloat16))
+    B, A, N, M = case.shape
+    b = 3
+    a_b = int(case.action[b].clamp(0, A - 1))
+    case.theta[b, a_b] = -1e4
+    case.taus[b] = 1.0
+    case.g[b] = 3.4e38
+    result = run_op(fn, case, 0.0, device)
+    assert bool((result[3][b, a_b].float() == -INF).all())
+    ref, bound = general_reference(case, 0.0)
+    assert bool((ref.grad[b] == -case.g[b].double()).all())
+    clean = clone_case(case)
+    clean.g[b] = 1.0
+    assert contained(run_op(fn, clean, 0.0, device), result, [b])
 
 
 class PixelQuantileNet(nn.Module):
