@@ -2,6 +2,7 @@ from .base import TorchFramework
 from .dqn import DQN
 from .dqn_per import DQNPer
 from .rainbow import RAINBOW
+from .iqn import IQN
 from .ddpg import DDPG
 from .hddpg import HDDPG
 from .td3 import TD3
@@ -26,6 +27,7 @@ __all__ = [
     "DQN",
     "DQNPer",
     "RAINBOW",
+    "IQN",
     "DDPG",
     "HDDPG",
     "TD3",

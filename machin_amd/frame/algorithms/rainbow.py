@@ -332,6 +332,15 @@ class RAINBOW(DQNPer):
             pred = dist[t.arange(B, device=device), action_index]  # [B,N]
             log_pred = t.log(pred.clamp_min(1e-8))
             per_sample = -(proj * log_pred).sum(dim=1)  # cross entropy
+        return self._apply_loss(per_sample, is_weight, index, update_value,
+                                update_target)
+
+    def _apply_loss(self, per_sample, is_weight, index, update_value,
+                    update_target):
+        """The tail of ``update``: importance weighting, priority
+        write-back, the optimizer step and the target update. Returns the
+        weighted mean loss as a float."""
+        B, device = per_sample.shape[0], per_sample.device
         weights = t.as_tensor(
             is_weight, dtype=per_sample.dtype, device=device
         ).view(B)

@@ -4,6 +4,7 @@ from .base import (
     static_module_wrapper,
 )
 from .gaussian import GaussianPolicyHead
+from .iqn import CosineTauEmbedding, ImplicitQuantileHead
 from .nature_cnn import ActorCriticCNN, NatureCNN, mlp
 from .noisy import (
     NoisyDuelingC51Head,
@@ -25,6 +26,8 @@ __all__ = [
     "GaussianPolicyHead",
     "NoisyLinear",
     "NoisyDuelingC51Head",
+    "CosineTauEmbedding",
+    "ImplicitQuantileHead",
     "reset_noise",
     "noise_enabled",
     "noisy_layers",

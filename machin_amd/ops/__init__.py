@@ -12,6 +12,7 @@ Dispatch policy: CUDA tensors REQUIRE the extension — if it is missing
 on a GPU machine we raise instead of silently falling back to eager
 torch, so a benchmark can never accidentally measure the fallback.
 """
+import math
 import os
 from typing import List, Optional, Sequence
 
@@ -1029,6 +1030,124 @@ def noisy_linear(x: t.Tensor, weight_mu: t.Tensor, weight_sigma: t.Tensor,
     )
 
 
+# ======================================================================
+# IQN: cosine embedding of sampled fractions, fused with the feature
+# ======================================================================
+IQN_EMBEDDING_MAX_COS = 64
+# With fewer than 32 fractions per sample (the backward's row tile, which
+# holds one sample's rows only) the kernels take at most this many
+# elements of psi (B * D); above it the torch form runs on the device.
+# Set from the measured table in docs/PERFORMANCE.md ("IQN embedding").
+IQN_EMBEDDING_FUSED_MAX_SMALL_N_FEATURES = 512 * 512
+
+
+def _iqn_embedding_check(psi, taus, weight, bias, psi_dtypes):
+    """Shared argument validation of :func:`iqn_embedding`; returns
+    ``(B, N, D, K)``."""
+    if psi.dtype not in psi_dtypes:
+        raise ValueError("psi must be float32 or bfloat16")
+    if psi.dim() != 2 or psi.numel() == 0:
+        raise ValueError("psi must be [B, D] and not empty")
+    B, D = psi.shape
+    if taus.dim() != 2 or taus.shape[0] != B or taus.shape[1] < 1:
+        raise ValueError(f"taus must be [{B}, N] with N >= 1")
+    if weight.dim() != 2 or weight.shape[0] != D:
+        raise ValueError(f"weight must be [{D}, K]")
+    K = weight.shape[1]
+    if not 1 <= K <= IQN_EMBEDDING_MAX_COS:
+        raise ValueError(f"K must be in [1, {IQN_EMBEDDING_MAX_COS}]")
+    if tuple(bias.shape) != (D,):
+        raise ValueError(f"bias must have shape ({D},)")
+    pdt = t.float64 if psi.dtype == t.float64 else t.float32
+    for name, p in (("taus", taus), ("weight", weight), ("bias", bias)):
+        if p.dtype != pdt:
+            raise ValueError(f"{name} must be {pdt}")
+        if p.device != psi.device:
+            raise ValueError(f"{name} must be on psi's device")
+    return B, taus.shape[1], D, K
+
+
+def _iqn_embedding_torch(psi, taus, weight, bias):
+    """Torch composition of :func:`iqn_embedding` (the CPU path and the
+    reference the kernels are tested and timed against). Computes in fp32
+    and returns psi's dtype, also inside a ``torch.autocast`` region
+    (autocast is switched off for the GEMM); float64 inputs are accepted
+    here (not by the kernels) and computed in float64, for gradient
+    checks."""
+    _, _, _, K = _iqn_embedding_check(
+        psi, taus, weight, bias, (t.float32, t.bfloat16, t.float64)
+    )
+    ct = t.float64 if psi.dtype == t.float64 else t.float32
+    taus = taus.detach()
+    with t.autocast(device_type=psi.device.type, enabled=False):
+        i = t.arange(K, device=psi.device, dtype=ct)
+        c = t.cos(math.pi * (taus.unsqueeze(-1) * i))
+        z = c @ weight.t() + bias
+        return (psi.to(ct).unsqueeze(1) * z.clamp_min(0)).to(psi.dtype)
+
+
+class _IQNEmbedding(t.autograd.Function):
+    @staticmethod
+    def forward(ctx, psi, taus, weight, bias):
+        psi, taus = psi.contiguous(), taus.contiguous()
+        weight, bias = weight.contiguous(), bias.contiguous()
+        h = _require_ext().iqn_embed_fwd(psi, taus, weight, bias)
+        ctx.save_for_backward(psi, taus, weight, bias)
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        psi, taus, weight, bias = ctx.saved_tensors
+        dpsi, dweight, dbias = _require_ext().iqn_embed_bwd(
+            g.to(psi.dtype).contiguous(), psi, taus, weight, bias
+        )
+        return dpsi, None, dweight, dbias
+
+
+def iqn_embedding(psi: t.Tensor, taus: t.Tensor, weight: t.Tensor,
+                  bias: t.Tensor) -> t.Tensor:
+    """Cosine embedding of sampled quantile fractions multiplied into
+    the state feature (Dabney et al., "Implicit Quantile Networks"):
+    returns ``h [B, N, D]``.
+
+    ``psi`` is ``[B, D]`` fp32 or bf16, ``taus`` fp32 ``[B, N]``,
+    ``weight`` fp32 ``[D, K]`` (the layout of ``nn.Linear(K, D)``,
+    ``1 <= K <= 64``) and ``bias`` fp32 ``[D]``. All arithmetic is fp32,
+    ``h`` takes ``psi``'s dtype with one rounding at the store::
+
+        a[b, n, i] = float(i) * taus[b, n]             (i = 0..K-1)
+        c[b, n, i] = cos(pi * a[b, n, i])
+        z[b, n, d] = sum_i c[b, n, i] * weight[d, i] + bias[d]
+        h[b, n, d] = psi[b, d] * max(z[b, n, d], 0)
+
+    Differentiable in ``psi``, ``weight`` and ``bias`` (not in
+    ``taus``)::
+
+        dpsi[b, d]    = sum_n dh[b, n, d] * max(z[b, n, d], 0)
+        e[b, n, d]    = dh[b, n, d] * psi[b, d] * [z[b, n, d] > 0]
+        dweight[d, i] = sum_{b, n} e[b, n, d] * c[b, n, i]
+        dbias[d]      = sum_{b, n} e[b, n, d]
+
+    On ROCm this is one gfx950 kernel forward and one backward plus a
+    small ordered reduction (machin_amd/ops/hip/iqn_embed.hip): the
+    cosine features are generated in registers in the fragment order of
+    the fp32 matrix instruction and neither ``c`` nor ``z`` is stored;
+    the backward recomputes ``z``. Sums have a fixed order, so results
+    are reproducible bit for bit. CPU tensors take the same semantics as
+    a torch composition, and so do device tensors with ``N < 32`` and
+    ``B * D > IQN_EMBEDDING_FUSED_MAX_SMALL_N_FEATURES``, where the
+    backward kernel measured slower.
+    """
+    if not psi.is_cuda:
+        return _iqn_embedding_torch(psi, taus, weight, bias)
+    B, N, D, _ = _iqn_embedding_check(
+        psi, taus, weight, bias, (t.float32, t.bfloat16)
+    )
+    if N < 32 and B * D > IQN_EMBEDDING_FUSED_MAX_SMALL_N_FEATURES:
+        return _iqn_embedding_torch(psi, taus, weight, bias)
+    return _IQNEmbedding.apply(psi, taus.detach(), weight, bias)
+
+
 def _factorised_noise_torch(buf: t.Tensor, seed: int, offset: int):
     gen = t.Generator(device="cpu")
     gen.manual_seed(
@@ -1927,6 +2046,7 @@ __all__ = [
     "c51_loss",
     "quantile_huber_loss",
     "noisy_linear",
+    "iqn_embedding",
     "factorised_noise_",
     "FusedPolyak",
     "FusedRMSprop",

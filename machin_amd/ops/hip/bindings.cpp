@@ -138,6 +138,15 @@ void factorised_noise_launch(float*, int64_t, uint64_t, uint64_t,
                              hipStream_t);
 int noisy_linear_slices(int64_t, int64_t, int64_t, int*);
 
+void iqn_embed_fwd_launch(const void*, const float*, const float*,
+                          const float*, void*, int, int, int, int, bool,
+                          hipStream_t);
+void iqn_embed_bwd_launch(const void*, const void*, const float*,
+                          const float*, const float*, void*, float*, float*,
+                          float*, float*, int, int, int, int, int, int, bool,
+                          hipStream_t);
+int iqn_embed_bwd_slices(int64_t, int64_t, int*);
+
 namespace {
 
 void check_f32_cuda(const Tensor& t, const char* name) {
@@ -449,6 +458,79 @@ std::vector<int64_t> noisy_linear_slices_py(int64_t B, int64_t N,
   int cps = 1;
   const int S = noisy_linear_slices(B, N, K, &cps);
   return {S, cps};
+}
+
+// ------------------------------------------------------------------
+// IQN cosine tau-embedding (semantics: machin_amd.ops.iqn_embedding)
+// ------------------------------------------------------------------
+// psi [B, D] fp32 / bf16; taus [B, N]; weight [D, K], K <= 64; bias [D]
+void check_iqn(const Tensor& psi, const Tensor& taus, const Tensor& weight,
+               const Tensor& bias) {
+  TORCH_CHECK(psi.is_cuda() && psi.is_contiguous() && psi.dim() == 2,
+              "psi must be a contiguous 2-D CUDA tensor");
+  TORCH_CHECK(psi.scalar_type() == at::kFloat ||
+                  psi.scalar_type() == at::kBFloat16,
+              "psi must be float32 or bfloat16");
+  TORCH_CHECK(taus.dim() == 2 && taus.size(0) == psi.size(0),
+              "taus must be [B, N] with psi's batch");
+  TORCH_CHECK(weight.dim() == 2 && weight.size(0) == psi.size(1),
+              "weight must be [D, K] with psi's D");
+  const int64_t B = psi.size(0), D = psi.size(1), N = taus.size(1),
+                K = weight.size(1);
+  TORCH_CHECK(K >= 1 && K <= 64, "K must be in [1, 64]");
+  TORCH_CHECK(B >= 1 && N >= 1 && D >= 1 && B * N < ((int64_t)1 << 31) &&
+                  D < ((int64_t)1 << 22),
+              "need B, N, D >= 1, B * N < 2^31 and D < 2^22");
+  check_arg(taus, psi, at::kFloat, B * N, "taus");
+  check_arg(weight, psi, at::kFloat, D * K, "weight");
+  check_arg(bias, psi, at::kFloat, D, "bias");
+}
+
+Tensor iqn_embed_fwd(Tensor psi, Tensor taus, Tensor weight, Tensor bias) {
+  check_iqn(psi, taus, weight, bias);
+  const int64_t B = psi.size(0), D = psi.size(1), N = taus.size(1),
+                K = weight.size(1);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(psi.device());
+  Tensor h = at::empty({B, N, D}, psi.options());
+  iqn_embed_fwd_launch(psi.data_ptr(), taus.data_ptr<float>(),
+                       weight.data_ptr<float>(), bias.data_ptr<float>(),
+                       h.data_ptr(), (int)(B * N), (int)N, (int)D, (int)K,
+                       psi.scalar_type() == at::kBFloat16, current_stream());
+  return h;
+}
+
+// Returns {dpsi [B, D] in psi's dtype, dweight [D, K], dbias [D]}.
+std::vector<Tensor> iqn_embed_bwd(Tensor g, Tensor psi, Tensor taus,
+                                  Tensor weight, Tensor bias) {
+  check_iqn(psi, taus, weight, bias);
+  const int64_t B = psi.size(0), D = psi.size(1), N = taus.size(1),
+                K = weight.size(1);
+  TORCH_CHECK(g.dim() == 3 && g.size(0) == B && g.size(1) == N &&
+                  g.size(2) == D,
+              "g must be [B, N, D]");
+  check_arg(g, psi, psi.scalar_type(), B * N * D, "g");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(psi.device());
+  const auto f32 = psi.options().dtype(at::kFloat);
+  Tensor dpsi = at::empty({B, D}, psi.options());
+  Tensor dweight = at::empty({D, K}, f32);
+  Tensor dbias = at::empty({D}, f32);
+  int per = 1;
+  const int S = iqn_embed_bwd_slices(B, D, &per);
+  Tensor part_w, part_b;
+  float *pw = nullptr, *pb = nullptr;
+  if (S > 1) {
+    part_w = at::empty({S, D, K}, f32);
+    part_b = at::empty({S, D}, f32);
+    pw = part_w.data_ptr<float>();
+    pb = part_b.data_ptr<float>();
+  }
+  iqn_embed_bwd_launch(g.data_ptr(), psi.data_ptr(), taus.data_ptr<float>(),
+                       weight.data_ptr<float>(), bias.data_ptr<float>(),
+                       dpsi.data_ptr(), dweight.data_ptr<float>(),
+                       dbias.data_ptr<float>(), pw, pb, (int)B, (int)N,
+                       (int)D, (int)K, per, S,
+                       psi.scalar_type() == at::kBFloat16, current_stream());
+  return {dpsi, dweight, dbias};
 }
 
 void factorised_noise_(Tensor buf, int64_t seed, int64_t offset) {
@@ -1446,6 +1528,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("noisy_linear_bwd_weight", &noisy_linear_bwd_weight);
   m.def("factorised_noise_", &factorised_noise_);
   m.def("noisy_linear_slices", &noisy_linear_slices_py);
+  m.def("iqn_embed_fwd", &iqn_embed_fwd);
+  m.def("iqn_embed_bwd", &iqn_embed_bwd);
   m.def("multi_tensor_polyak", &multi_tensor_polyak);
   m.def("multi_tensor_polyak_cached", &multi_tensor_polyak_cached);
   m.def("fused_rmsprop_cached", &fused_rmsprop_cached);

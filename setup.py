@@ -27,6 +27,7 @@ SOURCES = [
     "c51_loss.hip",
     "quantile_loss.hip",
     "noisy_linear.hip",
+    "iqn_embed.hip",
     "multi_tensor.hip",
     "distributions.hip",
     "elementwise.hip",
