@@ -887,6 +887,14 @@ def quantile_huber_loss(
 # two-GEMM torch form runs on the device. Set from the measured table in
 # docs/PERFORMANCE.md ("NoisyLinear").
 NOISY_LINEAR_FUSED_MAX_BATCH = 32
+# Fewest rows of bf16 x from which the split-weight MFMA kernels
+# (noisy_linear_mfma.hip) run instead of the torch form. The rule is the
+# smallest measured row count from which they are not slower than the
+# better eager form on every measured layer. In the table of
+# docs/PERFORMANCE.md no row count qualifies (they lose at 2048 and 4096
+# rows), so the value is above every row count the kernels accept and
+# the path never engages on its own; ``_NoisyLinearMFMA`` calls it.
+NOISY_LINEAR_MFMA_MIN_BATCH = 2 ** 31
 
 
 def _noisy_linear_check(x, weight_mu, weight_sigma, bias_mu, bias_sigma,
@@ -980,6 +988,43 @@ class _NoisyLinear(t.autograd.Function):
         return dx, dmu, dsigma, dbias_mu, dbias_sigma, None, None
 
 
+class _NoisyLinearMFMA(t.autograd.Function):
+    """:func:`noisy_linear` for bf16 ``x`` on the bf16 matrix unit
+    (machin_amd/ops/hip/noisy_linear_mfma.hip), any number of rows."""
+
+    @staticmethod
+    def forward(ctx, x, weight_mu, weight_sigma, bias_mu, bias_sigma,
+                eps_in, eps_out):
+        ext = _require_ext()
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        weight_mu = weight_mu.contiguous()
+        weight_sigma = weight_sigma.contiguous()
+        eps_in, eps_out = eps_in.contiguous(), eps_out.contiguous()
+        y = ext.noisy_linear_mfma_fwd(
+            x2, weight_mu, weight_sigma, bias_mu.contiguous(),
+            bias_sigma.contiguous(), eps_in, eps_out,
+        )
+        ctx.save_for_backward(x2, weight_mu, weight_sigma, eps_in, eps_out)
+        ctx.x_shape = x.shape
+        return y.view(*x.shape[:-1], weight_mu.shape[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        ext = _require_ext()
+        x2, weight_mu, weight_sigma, eps_in, eps_out = ctx.saved_tensors
+        g2 = g.reshape(-1, weight_mu.shape[0]).to(x2.dtype).contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.noisy_linear_mfma_bwd_input(
+                g2, weight_mu, weight_sigma, eps_in, eps_out
+            ).view(ctx.x_shape)
+        dmu = dsigma = dbias_mu = dbias_sigma = None
+        if any(ctx.needs_input_grad[1:5]):
+            dmu, dsigma, dbias_mu, dbias_sigma = \
+                ext.noisy_linear_mfma_bwd_weight(g2, x2, eps_in, eps_out)
+        return dx, dmu, dsigma, dbias_mu, dbias_sigma, None, None
+
+
 def noisy_linear(x: t.Tensor, weight_mu: t.Tensor, weight_sigma: t.Tensor,
                  bias_mu: t.Tensor, bias_sigma: t.Tensor, eps_in: t.Tensor,
                  eps_out: t.Tensor) -> t.Tensor:
@@ -1011,6 +1056,29 @@ def noisy_linear(x: t.Tensor, weight_mu: t.Tensor, weight_sigma: t.Tensor,
     accumulator. Sums have a fixed order, so results are reproducible
     bit for bit. Larger batches, and CPU tensors, take the two-GEMM torch
     form ``x @ mu.T + ((x * eps_in) @ sigma.T) * eps_out + bias``.
+
+    bf16 ``x`` of at least ``NOISY_LINEAR_MFMA_MIN_BATCH`` rows (as
+    measured today: no row count, see the constant) runs on the bf16
+    matrix unit instead
+    (machin_amd/ops/hip/noisy_linear_mfma.hip), with this arithmetic:
+
+    * ``w`` is composed in fp32 exactly as above and in the small-batch
+      kernels, and is never stored in global memory;
+    * ``w`` is split as ``hi = bf16_rne(w)``,
+      ``lo = bf16_rne(w - float(hi))`` (the subtraction is exact), so
+      with ``u = 2^-8``, ``|w - hi - lo| <= u^2 |w| = 2^-16 |w|``: the
+      weight keeps 16 significant bits;
+    * ``y`` and ``dx`` are ``sum a * hi + sum a * lo`` with fp32
+      accumulation in the matrix unit; the bias is added in fp32 and
+      the result is rounded to bf16 once, at the store;
+    * ``dmu = dy^T x`` has exact products (both factors are bf16) and
+      takes one pass; ``dsigma``, ``dbias_mu`` and ``dbias_sigma`` come
+      from the same sums with the formulas above;
+    * no atomics and a fixed order of every sum: two calls give equal
+      bits.
+
+    fp32 ``x`` never takes this path, and bf16 ``x`` with a row count
+    between the two limits takes the torch form.
     """
     if not x.is_cuda:
         return _noisy_linear_torch(
@@ -1020,7 +1088,14 @@ def noisy_linear(x: t.Tensor, weight_mu: t.Tensor, weight_sigma: t.Tensor,
         x, weight_mu, weight_sigma, bias_mu, bias_sigma, eps_in, eps_out,
         (t.float32, t.bfloat16),
     )
-    if x.numel() // I > NOISY_LINEAR_FUSED_MAX_BATCH:
+    rows = x.numel() // I
+    if x.dtype == t.bfloat16 and rows >= NOISY_LINEAR_MFMA_MIN_BATCH \
+            and rows > NOISY_LINEAR_FUSED_MAX_BATCH:
+        return _NoisyLinearMFMA.apply(
+            x, weight_mu, weight_sigma, bias_mu, bias_sigma,
+            eps_in.detach(), eps_out.detach(),
+        )
+    if rows > NOISY_LINEAR_FUSED_MAX_BATCH:
         return _noisy_linear_torch(
             x, weight_mu, weight_sigma, bias_mu, bias_sigma, eps_in, eps_out
         )

@@ -137,6 +137,18 @@ void noisy_linear_bwd_weight_launch(const void*, const void*, const float*,
 void factorised_noise_launch(float*, int64_t, uint64_t, uint64_t,
                              hipStream_t);
 int noisy_linear_slices(int64_t, int64_t, int64_t, int*);
+void noisy_linear_mfma_fwd_launch(const void*, const float*, const float*,
+                                  const float*, const float*, const float*,
+                                  const float*, void*, int, int, int,
+                                  hipStream_t);
+void noisy_linear_mfma_bwd_input_launch(const void*, const float*,
+                                        const float*, const float*,
+                                        const float*, void*, int, int, int,
+                                        hipStream_t);
+void noisy_linear_mfma_bwd_weight_launch(const void*, const void*,
+                                         const float*, const float*, float*,
+                                         float*, float*, float*, int, int,
+                                         int, hipStream_t);
 
 void iqn_embed_fwd_launch(const void*, const float*, const float*,
                           const float*, void*, int, int, int, int, bool,
@@ -458,6 +470,86 @@ std::vector<int64_t> noisy_linear_slices_py(int64_t B, int64_t N,
   int cps = 1;
   const int S = noisy_linear_slices(B, N, K, &cps);
   return {S, cps};
+}
+
+// ------------------------------------------------------------------
+// NoisyLinear on the bf16 matrix unit (noisy_linear_mfma.hip; semantics:
+// machin_amd.ops._NoisyLinearMFMA): bf16 x / dy, any R, I, O >= 1
+// ------------------------------------------------------------------
+// a is x [R, I] or dy [R, O]; tiles are 64 x 64, column tiles on grid.y
+void check_noisy_mfma(const Tensor& a, int64_t cols, const Tensor& mu,
+                      const Tensor& sigma, const Tensor& eps_in,
+                      const Tensor& eps_out, const char* name) {
+  check_noisy(a, cols, mu, sigma, eps_in, eps_out, name);
+  TORCH_CHECK(a.scalar_type() == at::kBFloat16, name, " must be bfloat16");
+  TORCH_CHECK(mu.size(0) <= 65535 * 64 && mu.size(1) <= 65535 * 64,
+              "I and O must be at most 4194240");
+}
+
+Tensor noisy_linear_mfma_fwd(Tensor x, Tensor mu, Tensor sigma,
+                             Tensor bias_mu, Tensor bias_sigma, Tensor eps_in,
+                             Tensor eps_out) {
+  TORCH_CHECK(mu.dim() == 2, "weight_mu must be [O, I]");
+  const int64_t O = mu.size(0), I = mu.size(1);
+  check_noisy_mfma(x, I, mu, sigma, eps_in, eps_out, "x");
+  check_arg(bias_mu, x, at::kFloat, O, "bias_mu");
+  check_arg(bias_sigma, x, at::kFloat, O, "bias_sigma");
+  const int64_t R = x.size(0);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({R, O}, x.options());
+  noisy_linear_mfma_fwd_launch(
+      x.data_ptr(), mu.data_ptr<float>(), sigma.data_ptr<float>(),
+      bias_mu.data_ptr<float>(), bias_sigma.data_ptr<float>(),
+      eps_in.data_ptr<float>(), eps_out.data_ptr<float>(), y.data_ptr(),
+      (int)R, (int)I, (int)O, current_stream());
+  return y;
+}
+
+Tensor noisy_linear_mfma_bwd_input(Tensor dy, Tensor mu, Tensor sigma,
+                                   Tensor eps_in, Tensor eps_out) {
+  TORCH_CHECK(mu.dim() == 2, "weight_mu must be [O, I]");
+  const int64_t O = mu.size(0), I = mu.size(1);
+  check_noisy_mfma(dy, O, mu, sigma, eps_in, eps_out, "dy");
+  const int64_t R = dy.size(0);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
+  Tensor dx = at::empty({R, I}, dy.options());
+  noisy_linear_mfma_bwd_input_launch(
+      dy.data_ptr(), mu.data_ptr<float>(), sigma.data_ptr<float>(),
+      eps_in.data_ptr<float>(), eps_out.data_ptr<float>(), dx.data_ptr(),
+      (int)R, (int)I, (int)O, current_stream());
+  return dx;
+}
+
+// Returns {dmu [O, I], dsigma [O, I], dbias_mu [O], dbias_sigma [O]}.
+std::vector<Tensor> noisy_linear_mfma_bwd_weight(Tensor dy, Tensor x,
+                                                 Tensor eps_in,
+                                                 Tensor eps_out) {
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 2,
+              "dy must be a contiguous 2-D CUDA tensor");
+  TORCH_CHECK(dy.scalar_type() == at::kBFloat16, "dy must be bfloat16");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) == dy.size(0),
+              "x must be [R, I] with dy's rows");
+  const int64_t R = dy.size(0), O = dy.size(1), I = x.size(1);
+  TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31) - 64 && O >= 1 && I >= 1 &&
+                  O * I < ((int64_t)1 << 31) && O <= 65535 * 64,
+              "need R, I, O >= 1, R < 2^31 - 64, O * I < 2^31 and "
+              "O <= 4194240");
+  check_arg(x, dy, at::kBFloat16, R * I, "x");
+  check_arg(eps_in, dy, at::kFloat, I, "eps_in");
+  check_arg(eps_out, dy, at::kFloat, O, "eps_out");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
+  const auto f32 = dy.options().dtype(at::kFloat);
+  Tensor dmu = at::empty({O, I}, f32);
+  Tensor dsigma = at::empty({O, I}, f32);
+  Tensor dbias_mu = at::empty({O}, f32);
+  Tensor dbias_sigma = at::empty({O}, f32);
+  noisy_linear_mfma_bwd_weight_launch(
+      dy.data_ptr(), x.data_ptr(), eps_in.data_ptr<float>(),
+      eps_out.data_ptr<float>(), dmu.data_ptr<float>(),
+      dsigma.data_ptr<float>(), dbias_mu.data_ptr<float>(),
+      dbias_sigma.data_ptr<float>(), (int)R, (int)I, (int)O,
+      current_stream());
+  return {dmu, dsigma, dbias_mu, dbias_sigma};
 }
 
 // ------------------------------------------------------------------
@@ -1528,6 +1620,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("noisy_linear_bwd_weight", &noisy_linear_bwd_weight);
   m.def("factorised_noise_", &factorised_noise_);
   m.def("noisy_linear_slices", &noisy_linear_slices_py);
+  m.def("noisy_linear_mfma_fwd", &noisy_linear_mfma_fwd);
+  m.def("noisy_linear_mfma_bwd_input", &noisy_linear_mfma_bwd_input);
+  m.def("noisy_linear_mfma_bwd_weight", &noisy_linear_mfma_bwd_weight);
   m.def("iqn_embed_fwd", &iqn_embed_fwd);
   m.def("iqn_embed_bwd", &iqn_embed_bwd);
   m.def("multi_tensor_polyak", &multi_tensor_polyak);

@@ -27,6 +27,7 @@ SOURCES = [
     "c51_loss.hip",
     "quantile_loss.hip",
     "noisy_linear.hip",
+    "noisy_linear_mfma.hip",
     "iqn_embed.hip",
     "multi_tensor.hip",
     "distributions.hip",

@@ -18,6 +18,18 @@ is timed on the GPU in three forms:
 * two_gemm — ``ops._noisy_linear_torch`` on the device:
              ``x @ mu.T + ((x * eps_in) @ sigma.T) * eps_out + b``.
 
+For bf16 ``x`` a fourth form is timed in the same rounds:
+
+* mfma     — ``ops._NoisyLinearMFMA``
+             (machin_amd/ops/hip/noisy_linear_mfma.hip: split-weight
+             bf16 MFMA forward, input-gradient and weight-gradient
+             kernels), at every B, whatever
+             ``ops.NOISY_LINEAR_MFMA_MIN_BATCH`` is.
+
+The two noisy layers of the IQN pixel head at its row count (32 samples
+x 64 fractions: ``2048 x 3136->512`` and ``2048 x 512->6``) are timed
+next to the Rainbow layers.
+
 Then ``reset_noise`` on a ``NoisyDuelingC51Head(512, 6, 51)`` (4 layers,
 one ``ops.factorised_noise_`` launch each) is timed against the torch
 chain ``randn, sign, abs, sqrt, mul`` per noise vector (8 vectors, 40
@@ -49,6 +61,7 @@ from machin_amd.model.nets import NoisyDuelingC51Head, noisy_layers, \
     reset_noise
 
 LAYERS = ((3136, 512), (512, 306), (512, 51))
+IQN_CASES = ((3136, 512, 2048), (512, 6, 2048))  # (I, O, rows)
 FORMS = ("fused", "composed", "two_gemm")
 
 
@@ -99,44 +112,50 @@ def summarise(row, samples):
 def bench_layers(args, dev):
     rows = []
     forms = {"fused": ops._NoisyLinear.apply, "composed": composed,
-             "two_gemm": ops._noisy_linear_torch}
+             "two_gemm": ops._noisy_linear_torch,
+             "mfma": ops._NoisyLinearMFMA.apply}
+    cases = [(I, O, B) for I, O in LAYERS for B in args.batches]
+    cases += list(IQN_CASES)
     for dtype in (t.float32, t.bfloat16):
-        for I, O in LAYERS:
-            for B in args.batches:
-                x, dy, params, eps = make_inputs(B, I, O, dtype, dev)
+        names = FORMS + (("mfma",) if dtype == t.bfloat16 else ())
+        for I, O, B in cases:
+            x, dy, params, eps = make_inputs(B, I, O, dtype, dev)
 
-                def step(form):
-                    def run():
-                        y = form(x, *params, *eps)
-                        return (y,) + t.autograd.grad(y, [x] + params, dy)
-                    return run
+            def step(form):
+                def run():
+                    y = form(x, *params, *eps)
+                    return (y,) + t.autograd.grad(y, [x] + params, dy)
+                return run
 
-                variants = [(name, step(forms[name])) for name in FORMS]
-                if dtype == t.float32:
-                    want = variants[0][1]()
-                    for _, fn in variants[1:]:
-                        for a, b in zip(fn(), want):
-                            atol = 1e-4 * float(b.abs().max())
-                            assert t.allclose(a, b, rtol=1e-4, atol=atol)
-                for _, fn in variants:
-                    time_ms(fn, 10)  # warm-up
-                samples = {name: [] for name, _ in variants}
-                for _ in range(args.rounds):
-                    for name, fn in variants:
-                        samples[name].append(time_ms(fn, args.iters))
-                row = {"dtype": str(dtype).split(".")[1], "I": I, "O": O,
-                       "B": B, "iters": args.iters, "rounds": args.rounds}
-                summarise(row, samples)
-                best = min(row["composed_ms"], row["two_gemm_ms"])
-                row["best_eager_over_fused"] = best / row["fused_ms"]
-                # fused is "not slower" when it loses by no more than
-                # the rounds' min-max spread
-                spread = max(
-                    row[n + "_max_ms"] - row[n + "_min_ms"] for n in FORMS
-                )
-                row["fused_not_slower"] = row["fused_ms"] <= best + spread
-                rows.append(row)
-                print(json.dumps(row), flush=True)
+            variants = [(name, step(forms[name])) for name in names]
+            if dtype == t.float32:
+                want = variants[0][1]()
+                for _, fn in variants[1:]:
+                    for a, b in zip(fn(), want):
+                        atol = 1e-4 * float(b.abs().max())
+                        assert t.allclose(a, b, rtol=1e-4, atol=atol)
+            for _, fn in variants:
+                time_ms(fn, 10)  # warm-up
+            samples = {name: [] for name, _ in variants}
+            for _ in range(args.rounds):
+                for name, fn in variants:
+                    samples[name].append(time_ms(fn, args.iters))
+            row = {"dtype": str(dtype).split(".")[1], "I": I, "O": O,
+                   "B": B, "iters": args.iters, "rounds": args.rounds}
+            summarise(row, samples)
+            best = min(row["composed_ms"], row["two_gemm_ms"])
+            row["best_eager_over_fused"] = best / row["fused_ms"]
+            # fused is "not slower" when it loses by no more than
+            # the rounds' min-max spread
+            spread = max(
+                row[n + "_max_ms"] - row[n + "_min_ms"] for n in names
+            )
+            row["fused_not_slower"] = row["fused_ms"] <= best + spread
+            if "mfma" in names:
+                row["best_eager_over_mfma"] = best / row["mfma_ms"]
+                row["mfma_not_slower"] = row["mfma_ms"] <= best + spread
+            rows.append(row)
+            print(json.dumps(row), flush=True)
     return rows
 
 
@@ -191,15 +210,19 @@ def main():
 
     lines = [
         "| x | layer | B | fused ms (min-max) | composed ms | two-GEMM ms | "
-        "best eager / fused | fused not slower |",
-        "|---|---|---|---|---|---|---|---|",
+        "best eager / fused | fused not slower | mfma ms | "
+        "best eager / mfma | mfma not slower |",
+        "|---|---|---|---|---|---|---|---|---|---|---|",
     ]
     for r in rows:
         lines.append(
             f"| {r['dtype']} | {r['I']}->{r['O']} | {r['B']} | "
             f"{cell(r, 'fused')} | {cell(r, 'composed')} | "
             f"{cell(r, 'two_gemm')} | {r['best_eager_over_fused']:.2f}x | "
-            f"{'yes' if r['fused_not_slower'] else 'no'} |"
+            f"{'yes' if r['fused_not_slower'] else 'no'} | "
+            + (f"{cell(r, 'mfma')} | {r['best_eager_over_mfma']:.2f}x | "
+               f"{'yes' if r['mfma_not_slower'] else 'no'} |"
+               if "mfma_ms" in r else "- | - | - |")
         )
     lines += [
         "",
