@@ -83,19 +83,27 @@ class FusedActorCriticCNN(NeuralNetworkModule):
     activation already flattened for the fc layer. Results are
     bit-identical to ActorCriticCNN's conv + ReLU composition under
     bf16 autocast; parameter names are the same (the ``nn.Identity``
-    entries keep the ``Sequential`` indices of the former ReLUs)."""
+    entries keep the ``Sequential`` indices of the former ReLUs).
 
-    def __init__(self, action_num: int = 6, feature_dim: int = 512):
+    ``conv_impl`` is handed to both ConvBiasReLU2d layers as their
+    ``impl``: ``"hip"`` runs conv2 and conv3 forward and their input
+    gradients as hand-written implicit-GEMM kernels, which round once
+    where MIOpen's composition rounds twice (not bit-identical);
+    ``None`` follows ``MACHIN_CONV_IMPL``, default ``"miopen"``."""
+
+    def __init__(self, action_num: int = 6, feature_dim: int = 512,
+                 conv_impl=None):
         super().__init__()
         from ...ops.fused_conv import ConvBiasReLU2d, FusedAtariConv1
 
         self.stem = FusedAtariConv1(relu=True)
         self.conv_rest = nn.Sequential(
-            ConvBiasReLU2d(32, 64, 4, stride=2),
+            ConvBiasReLU2d(32, 64, 4, stride=2, impl=conv_impl),
             nn.Identity(),
             # hands the fc its [N, 3136] input directly: no layout
             # copy around the (now no-op) Flatten below
-            ConvBiasReLU2d(64, 64, 3, stride=1, flatten=True),
+            ConvBiasReLU2d(64, 64, 3, stride=1, flatten=True,
+                           impl=conv_impl),
             nn.Identity(),
         )
         self.fc = nn.Sequential(

@@ -248,22 +248,166 @@ def bias_relu(y: t.Tensor, bias: t.Tensor,
     return out.flatten(1) if flatten else out
 
 
+_CONV_IMPLS = ("miopen", "hip")
+
+
+def _igemm_weights(weight: t.Tensor, stride: int):
+    """The two repacks the implicit-GEMM kernels read, both with the
+    reduction index last, running (tap row, tap column, channel) as the
+    resident image does.
+
+    Forward: ``[Cout, KH*KW*Cin]``. Data gradient: one slice per parity
+    class ``(py, px)`` of the input pixel, ``[S*S, Cin, T*T*Cout]`` with
+    ``T = KH / S``; window position ``(j, i)`` of class ``(py, px)`` is
+    the tap ``(py + S (T-1-j), px + S (T-1-i))``."""
+    cout, cin, kh, kw = weight.shape
+    w = weight.detach().to(t.bfloat16)
+    w_fwd = w.permute(0, 2, 3, 1).reshape(cout, kh * kw * cin).contiguous()
+    tt = kh // stride
+    w_bwd = (
+        w.reshape(cout, cin, tt, stride, tt, stride).flip(2, 4)
+        .permute(3, 5, 1, 2, 4, 0)
+        .reshape(stride * stride, cin, tt * tt * cout).contiguous()
+    )
+    return w_fwd, w_bwd
+
+
+class _ConvBiasReLUIgemmFn(t.autograd.Function):
+    """relu(conv(x, weight) + bias) by the implicit-GEMM kernels
+    (``ops/hip/conv_igemm.hip``): forward and input gradient hand-written,
+    ReLU mask and bias gradient by the bias+ReLU backward kernels on the
+    saved activation, weight gradient by ATen."""
+
+    @staticmethod
+    def forward(ctx, x: t.Tensor, weight: t.Tensor, bias: t.Tensor,
+                stride: int, flatten: bool):
+        ext = _require_ext()
+        N, _, H, W = x.shape
+        cout, _, k, _ = weight.shape
+        w_fwd, w_bwd = _igemm_weights(weight, stride)
+        out = ext.conv_igemm_fwd(
+            x.permute(0, 2, 3, 1), w_fwd, _bias_f32(bias), k, stride,
+            flatten,
+        )
+        OH, OW = (H - k) // stride + 1, (W - k) // stride + 1
+        if not flatten:
+            out = out.view(N, OH, OW, cout).permute(0, 3, 1, 2)
+        ctx.save_for_backward(x, weight, w_bwd, out)
+        ctx.geom = (k, stride, flatten, OH, OW)
+        ctx.bias_dtype = bias.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, gy: t.Tensor):
+        ext = _require_ext()
+        x, weight, w_bwd, out = ctx.saved_tensors
+        k, stride, flatten, OH, OW = ctx.geom
+        N, _, H, W = x.shape
+        cout = weight.shape[0]
+        if flatten:
+            g_rows, grad_b = ext.bias_relu_flat_bwd(
+                gy.to(t.bfloat16).contiguous(), out, cout
+            )
+        else:
+            gy_cl = gy.to(t.bfloat16).contiguous(
+                memory_format=t.channels_last
+            )
+            g_rows, grad_b = ext.bias_relu_bwd(
+                _rows_view(gy_cl), _rows_view(out)
+            )
+        g = g_rows.view(N, OH, OW, cout)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.conv_igemm_bwd_data(
+                g, w_bwd, k, stride, H, W
+            ).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            dw = t.ops.aten.convolution_backward(
+                g.permute(0, 3, 1, 2), x, weight, None, [stride, stride],
+                [0, 0], [1, 1], False, [0, 0], 1, [False, True, False],
+            )[1]
+        return dx, dw, grad_b.to(ctx.bias_dtype), None, None
+
+
 class ConvBiasReLU2d(nn.Conv2d):
     """``nn.Conv2d`` followed by ReLU, with the bias add, the ReLU and
     their backward fused into one pass each way (see
     :func:`bias_relu`). Same parameters, names and initialisation as
     ``nn.Conv2d``. With ``flatten=True`` the module returns the
     flattened ``[N, C*H*W]`` activation (a following ``nn.Flatten`` is
-    then a no-op)."""
+    then a no-op).
 
-    def __init__(self, *args, flatten: bool = False, **kwargs):
+    ``impl`` chooses who runs the convolution. ``"miopen"`` is the
+    composition above. ``"hip"`` runs the forward, with the bias and
+    the ReLU in its epilogue, and the input gradient as hand-written
+    gfx950 implicit-GEMM kernels when the call is eligible: a CUDA
+    bf16 (or bf16-autocast) channels-last 16-byte aligned input, no
+    padding, dilation or groups, one of the two Nature geometries
+    (32 -> 64, 4x4, stride 2; 64 -> 64, 3x3, stride 1), an image small
+    enough for the kernels' LDS buffers, extension loaded. Any other
+    call takes the ``"miopen"`` path. ``None`` reads the environment
+    variable ``MACHIN_CONV_IMPL`` at call time (default ``"miopen"``).
+
+    The two paths do not round alike. ``"hip"`` computes
+    ``relu(bf16(acc + bias))`` with the fp32 accumulator and the fp32
+    bias, ONE rounding, as the stem does; ``"miopen"`` computes
+    ``relu(bf16(bf16(conv) + bf16(bias)))``, what ``F.conv2d`` with a
+    bias gives under bf16 autocast. That is why ``"hip"`` is opt-in."""
+
+    def __init__(self, *args, flatten: bool = False, impl=None, **kwargs):
         super().__init__(*args, **kwargs)
+        if impl is not None and impl not in _CONV_IMPLS:
+            raise ValueError(
+                f"impl must be None or one of {_CONV_IMPLS}, got {impl!r}"
+            )
         self.flatten = flatten
+        self.impl = impl
+
+    def _igemm_input(self, x: t.Tensor):
+        """``(x, weight)`` as the implicit-GEMM path takes them, or None
+        when the call is not eligible."""
+        if not (x.is_cuda and x.dim() == 4 and x.shape[0] > 0
+                and self.padding == (0, 0) and self.dilation == (1, 1)
+                and self.groups == 1
+                and self.kernel_size[0] == self.kernel_size[1]
+                and self.stride[0] == self.stride[1]):
+            return None
+        weight = self.weight
+        if t.is_autocast_enabled("cuda") and \
+                t.get_autocast_dtype("cuda") == t.bfloat16:
+            # the casts ATen's autocast makes in front of a convolution
+            x, weight = x.to(t.bfloat16), weight.to(t.bfloat16)
+        ext = _load_ext()
+        if not (ext is not None
+                and x.dtype == t.bfloat16 and weight.dtype == t.bfloat16
+                and x.is_contiguous(memory_format=t.channels_last)
+                and x.data_ptr() % 16 == 0
+                and ext.conv_igemm_fits(
+                    self.in_channels, self.out_channels,
+                    self.kernel_size[0], self.stride[0],
+                    x.shape[2], x.shape[3])):
+            return None
+        return x, weight
 
     def forward(self, x: t.Tensor) -> t.Tensor:
+        impl = self.impl
+        if impl is None:
+            impl = os.environ.get("MACHIN_CONV_IMPL", "miopen")
+            if impl not in _CONV_IMPLS:
+                raise ValueError(
+                    f"MACHIN_CONV_IMPL must be one of {_CONV_IMPLS}, "
+                    f"got {impl!r}"
+                )
         if self.padding_mode != "zeros" or self.bias is None:
             out = F.relu(super().forward(x))
             return out.flatten(1) if self.flatten else out
+        if impl == "hip":
+            args = self._igemm_input(x)
+            if args is not None:
+                return _ConvBiasReLUIgemmFn.apply(
+                    args[0], args[1], self.bias, self.stride[0],
+                    self.flatten,
+                )
         y = F.conv2d(x, self.weight, None, self.stride, self.padding,
                      self.dilation, self.groups)
         return bias_relu(y, self.bias, self.flatten)

@@ -122,6 +122,12 @@ void bias_relu_flat_launch(const void*, const float*, void*, int64_t, int,
                            int, hipStream_t);
 void bias_relu_flat_bwd_launch(const void*, const void*, void*, float*,
                                float*, int64_t, int, int, hipStream_t);
+int conv_igemm_geometry(int64_t, int64_t, int64_t, int64_t);
+int conv_igemm_group(int, int64_t, int64_t, int);
+void conv_igemm_fwd_launch(int, const void*, const void*, const float*,
+                           void*, int64_t, int, int, int, hipStream_t);
+void conv_igemm_bwd_data_launch(int, const void*, const void*, void*,
+                                int64_t, int, int, hipStream_t);
 
 void noisy_linear_fwd_launch(const void*, const float*, const float*,
                              const float*, const float*, const float*,
@@ -1601,6 +1607,87 @@ Tensor mfma_probe(Tensor A, Tensor B) {
 
 }  // namespace
 
+// ------------------------------------------------------------------
+// implicit-GEMM conv2/conv3 (conv_igemm.hip)
+// ------------------------------------------------------------------
+void check_nhwc_bf16(const Tensor& t, int64_t C, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+                  t.dim() == 4 && t.is_contiguous() && t.size(3) == C,
+              name, " must be a contiguous [N, H, W, ", C,
+              "] bf16 CUDA tensor");
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, name,
+              " must be 16-byte aligned");
+}
+
+void check_igemm_weight(const Tensor& w, const Tensor& like, int64_t numel) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 &&
+                  w.is_contiguous() && w.numel() == numel &&
+                  w.device() == like.device(),
+              "weight must be the contiguous bf16 repack of ", numel,
+              " elements on the input's device");
+  TORCH_CHECK((uintptr_t)w.data_ptr() % 16 == 0,
+              "weight must be 16-byte aligned");
+}
+
+// Whether the forward and the data gradient of this layer on H x W
+// inputs are served by the implicit-GEMM kernels (geometry in the table
+// and at least one sample fits the LDS buffers each way).
+bool conv_igemm_fits(int64_t cin, int64_t cout, int64_t ksize,
+                     int64_t stride, int64_t H, int64_t W) {
+  const int geom = conv_igemm_geometry(cin, cout, ksize, stride);
+  return geom >= 0 && conv_igemm_group(geom, H, W, 0) >= 1 &&
+         conv_igemm_group(geom, H, W, 1) >= 1;
+}
+
+// relu(bf16(conv(x, w) + bias)) for x [N, H, W, Cin] bf16 and the
+// weight repack [Cout, ksize*ksize*Cin] (tap row, tap column, channel);
+// returns channels-last rows [N*OH*OW, Cout], or with flatten the
+// NCHW-flattened [N, Cout*OH*OW].
+Tensor conv_igemm_fwd(Tensor x, Tensor w, Tensor bias, int64_t ksize,
+                      int64_t stride, bool flatten) {
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 2, "x must be 4-d and w 2-d");
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2);
+  const int64_t cin = x.size(3), cout = w.size(0);
+  const int geom = conv_igemm_geometry(cin, cout, ksize, stride);
+  TORCH_CHECK(geom >= 0 && conv_igemm_group(geom, H, W, 0) >= 1,
+              "conv_igemm_fwd: geometry or image size not eligible");
+  check_nhwc_bf16(x, cin, "x");
+  check_igemm_weight(w, x, cout * ksize * ksize * cin);
+  check_f32_cuda(bias, "bias");
+  TORCH_CHECK(bias.numel() == cout && bias.device() == x.device(),
+              "bias must have Cout elements on x's device");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  const int64_t OH = (H - ksize) / stride + 1, OW = (W - ksize) / stride + 1;
+  Tensor out = flatten ? at::empty({N, cout * OH * OW}, x.options())
+                       : at::empty({N * OH * OW, cout}, x.options());
+  conv_igemm_fwd_launch(geom, x.data_ptr(), w.data_ptr(),
+                        bias.data_ptr<float>(), out.data_ptr(), N, (int)H,
+                        (int)W, flatten ? 1 : 0, current_stream());
+  return out;
+}
+
+// dx [N, H, W, Cin] for g [N, OH, OW, Cout] bf16 and the class repack
+// of the weight [stride*stride, Cin, (ksize/stride)^2 * Cout].
+Tensor conv_igemm_bwd_data(Tensor g, Tensor w, int64_t ksize,
+                           int64_t stride, int64_t H, int64_t W) {
+  TORCH_CHECK(g.dim() == 4 && w.dim() == 3, "g must be 4-d and w 3-d");
+  const int64_t N = g.size(0), cout = g.size(3), cin = w.size(1);
+  const int geom = conv_igemm_geometry(cin, cout, ksize, stride);
+  TORCH_CHECK(geom >= 0 && conv_igemm_group(geom, H, W, 1) >= 1,
+              "conv_igemm_bwd_data: geometry or image size not eligible");
+  TORCH_CHECK(g.size(1) == (H - ksize) / stride + 1 &&
+                  g.size(2) == (W - ksize) / stride + 1,
+              "g must be the conv output's shape for H x W inputs");
+  check_nhwc_bf16(g, cout, "g");
+  check_igemm_weight(w, g, cout * ksize * ksize * cin);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
+  Tensor dx = at::empty({N, H, W, cin}, g.options());
+  conv_igemm_bwd_data_launch(geom, g.data_ptr(), w.data_ptr(),
+                             dx.data_ptr(), N, (int)H, (int)W,
+                             current_stream());
+  return dx;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "machin_amd gfx950 HIP kernels";
   m.def("sumtree_update", &sumtree_update);
@@ -1655,4 +1742,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_relu_bwd", &bias_relu_bwd);
   m.def("bias_relu_flat", &bias_relu_flat);
   m.def("bias_relu_flat_bwd", &bias_relu_flat_bwd);
+  m.def("conv_igemm_fits", &conv_igemm_fits);
+  m.def("conv_igemm_fwd", &conv_igemm_fwd);
+  m.def("conv_igemm_bwd_data", &conv_igemm_bwd_data);
 }

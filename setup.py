@@ -37,6 +37,7 @@ SOURCES = [
     "pixelcatch.hip",
     "conv1_wrw.hip",
     "bias_act.hip",
+    "conv_igemm.hip",
 ]
 # Per-source flags. quantile_loss.hip is scalar fp32 VALU code whose sums
 # have a fixed order; it is compiled without the packed fp32 instructions
