@@ -89,6 +89,7 @@ class FusedActorCriticCNN(NeuralNetworkModule):
     ``impl``: ``"hip"`` runs conv2 and conv3 forward and their input
     gradients as hand-written implicit-GEMM kernels, which round once
     where MIOpen's composition rounds twice (not bit-identical);
+    ``"hip_wrw"`` adds their weight gradients as a hand-written kernel;
     ``None`` follows ``MACHIN_CONV_IMPL``, default ``"miopen"``."""
 
     def __init__(self, action_num: int = 6, feature_dim: int = 512,

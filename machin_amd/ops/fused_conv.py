@@ -248,7 +248,7 @@ def bias_relu(y: t.Tensor, bias: t.Tensor,
     return out.flatten(1) if flatten else out
 
 
-_CONV_IMPLS = ("miopen", "hip")
+_CONV_IMPLS = ("miopen", "hip", "hip_wrw")
 
 
 def _igemm_weights(weight: t.Tensor, stride: int):
@@ -299,34 +299,50 @@ class _ConvBiasReLUIgemmFn(t.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy: t.Tensor):
-        ext = _require_ext()
-        x, weight, w_bwd, out = ctx.saved_tensors
-        k, stride, flatten, OH, OW = ctx.geom
-        N, _, H, W = x.shape
-        cout = weight.shape[0]
-        if flatten:
-            g_rows, grad_b = ext.bias_relu_flat_bwd(
-                gy.to(t.bfloat16).contiguous(), out, cout
-            )
-        else:
-            gy_cl = gy.to(t.bfloat16).contiguous(
-                memory_format=t.channels_last
-            )
-            g_rows, grad_b = ext.bias_relu_bwd(
-                _rows_view(gy_cl), _rows_view(out)
-            )
-        g = g_rows.view(N, OH, OW, cout)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = ext.conv_igemm_bwd_data(
-                g, w_bwd, k, stride, H, W
-            ).permute(0, 3, 1, 2)
-        if ctx.needs_input_grad[1]:
-            dw = t.ops.aten.convolution_backward(
-                g.permute(0, 3, 1, 2), x, weight, None, [stride, stride],
-                [0, 0], [1, 1], False, [0, 0], 1, [False, True, False],
-            )[1]
-        return dx, dw, grad_b.to(ctx.bias_dtype), None, None
+        return _igemm_backward(ctx, gy, False)
+
+
+class _ConvBiasReLUIgemmWrwFn(_ConvBiasReLUIgemmFn):
+    """:class:`_ConvBiasReLUIgemmFn` with the weight gradient hand-written
+    too (``ops/hip/conv_igemm_wrw.hip``): fp32 sums in a fixed order over
+    the masked bf16 gradient, rounded once."""
+
+    @staticmethod
+    def backward(ctx, gy: t.Tensor):
+        return _igemm_backward(ctx, gy, True)
+
+
+def _igemm_backward(ctx, gy: t.Tensor, hand_wrw: bool):
+    ext = _require_ext()
+    x, weight, w_bwd, out = ctx.saved_tensors
+    k, stride, flatten, OH, OW = ctx.geom
+    N, _, H, W = x.shape
+    cout = weight.shape[0]
+    if flatten:
+        g_rows, grad_b = ext.bias_relu_flat_bwd(
+            gy.to(t.bfloat16).contiguous(), out, cout
+        )
+    else:
+        gy_cl = gy.to(t.bfloat16).contiguous(
+            memory_format=t.channels_last
+        )
+        g_rows, grad_b = ext.bias_relu_bwd(
+            _rows_view(gy_cl), _rows_view(out)
+        )
+    g = g_rows.view(N, OH, OW, cout)
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        dx = ext.conv_igemm_bwd_data(
+            g, w_bwd, k, stride, H, W
+        ).permute(0, 3, 1, 2)
+    if ctx.needs_input_grad[1] and hand_wrw:
+        dw = ext.conv_igemm_wrw(g, x.permute(0, 2, 3, 1), k, stride)
+    elif ctx.needs_input_grad[1]:
+        dw = t.ops.aten.convolution_backward(
+            g.permute(0, 3, 1, 2), x, weight, None, [stride, stride],
+            [0, 0], [1, 1], False, [0, 0], 1, [False, True, False],
+        )[1]
+    return dx, dw, grad_b.to(ctx.bias_dtype), None, None
 
 
 class ConvBiasReLU2d(nn.Conv2d):
@@ -345,8 +361,13 @@ class ConvBiasReLU2d(nn.Conv2d):
     padding, dilation or groups, one of the two Nature geometries
     (32 -> 64, 4x4, stride 2; 64 -> 64, 3x3, stride 1), an image small
     enough for the kernels' LDS buffers, extension loaded. Any other
-    call takes the ``"miopen"`` path. ``None`` reads the environment
-    variable ``MACHIN_CONV_IMPL`` at call time (default ``"miopen"``).
+    call takes the ``"miopen"`` path. ``"hip_wrw"`` is ``"hip"`` plus
+    the weight gradient as a hand-written kernel too
+    (``ops/hip/conv_igemm_wrw.hip``: fp32 sums in a fixed order, no
+    atomics, one rounding) where the image also fits that kernel's
+    buffers; a call eligible for ``"hip"`` only runs exactly as
+    ``"hip"``. ``None`` reads the environment variable
+    ``MACHIN_CONV_IMPL`` at call time (default ``"miopen"``).
 
     The two paths do not round alike. ``"hip"`` computes
     ``relu(bf16(acc + bias))`` with the fp32 accumulator and the fp32
@@ -401,10 +422,16 @@ class ConvBiasReLU2d(nn.Conv2d):
         if self.padding_mode != "zeros" or self.bias is None:
             out = F.relu(super().forward(x))
             return out.flatten(1) if self.flatten else out
-        if impl == "hip":
+        if impl != "miopen":
             args = self._igemm_input(x)
             if args is not None:
-                return _ConvBiasReLUIgemmFn.apply(
+                fn = _ConvBiasReLUIgemmFn
+                if impl == "hip_wrw" and _load_ext().conv_igemm_wrw_fits(
+                        self.in_channels, self.out_channels,
+                        self.kernel_size[0], self.stride[0],
+                        x.shape[2], x.shape[3]):
+                    fn = _ConvBiasReLUIgemmWrwFn
+                return fn.apply(
                     args[0], args[1], self.bias, self.stride[0],
                     self.flatten,
                 )

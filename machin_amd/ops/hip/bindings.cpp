@@ -128,6 +128,10 @@ void conv_igemm_fwd_launch(int, const void*, const void*, const float*,
                            void*, int64_t, int, int, int, hipStream_t);
 void conv_igemm_bwd_data_launch(int, const void*, const void*, void*,
                                 int64_t, int, int, hipStream_t);
+int conv_igemm_wrw_group(int, int64_t, int64_t);
+int64_t conv_igemm_wrw_slabs(int, int64_t, int64_t, int64_t);
+void conv_igemm_wrw_launch(int, const void*, const void*, float*, int64_t,
+                           void*, int64_t, int, int, hipStream_t);
 
 void noisy_linear_fwd_launch(const void*, const float*, const float*,
                              const float*, const float*, const float*,
@@ -1688,6 +1692,49 @@ Tensor conv_igemm_bwd_data(Tensor g, Tensor w, int64_t ksize,
   return dx;
 }
 
+// Whether the weight gradient of this layer on H x W inputs is served by
+// conv_igemm_wrw.hip (geometry in the table and at least one sample fits
+// its prefetch registers and LDS planes).
+bool conv_igemm_wrw_fits(int64_t cin, int64_t cout, int64_t ksize,
+                         int64_t stride, int64_t H, int64_t W) {
+  const int geom = conv_igemm_geometry(cin, cout, ksize, stride);
+  return geom >= 0 && conv_igemm_wrw_group(geom, H, W) >= 1;
+}
+
+// dW [Cout, Cin, ksize, ksize] bf16 for the (masked) gradient
+// g [N, OH, OW, Cout] and the input x [N, H, W, Cin], both bf16
+// channels-last rows: fp32 accumulation, one rounding, no atomics.
+Tensor conv_igemm_wrw(Tensor g, Tensor x, int64_t ksize, int64_t stride) {
+  TORCH_CHECK(g.dim() == 4 && x.dim() == 4, "g and x must be 4-d");
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2);
+  const int64_t cin = x.size(3), cout = g.size(3);
+  const int geom = conv_igemm_geometry(cin, cout, ksize, stride);
+  TORCH_CHECK(geom >= 0 && conv_igemm_wrw_group(geom, H, W) >= 1,
+              "conv_igemm_wrw: geometry or image size not eligible");
+  TORCH_CHECK(g.size(0) == N && g.size(1) == (H - ksize) / stride + 1 &&
+                  g.size(2) == (W - ksize) / stride + 1,
+              "g must be the conv output's shape for x");
+  TORCH_CHECK(g.device() == x.device(), "g and x must be on one device");
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  if (N == 0) {
+    TORCH_CHECK(g.is_cuda() && x.is_cuda() &&
+                    g.scalar_type() == at::kBFloat16 &&
+                    x.scalar_type() == at::kBFloat16,
+                "g and x must be bf16 CUDA tensors");
+    return at::zeros({cout, cin, ksize, ksize}, x.options());
+  }
+  check_nhwc_bf16(g, cout, "g");
+  check_nhwc_bf16(x, cin, "x");
+  const int64_t slabs = conv_igemm_wrw_slabs(geom, N, H, W);
+  Tensor slab = at::empty({slabs, cout, ksize * ksize * cin},
+                          x.options().dtype(at::kFloat));
+  Tensor dw = at::empty({cout, cin, ksize, ksize}, x.options());
+  conv_igemm_wrw_launch(geom, g.data_ptr(), x.data_ptr(),
+                        slab.data_ptr<float>(), slabs, dw.data_ptr(), N,
+                        (int)H, (int)W, current_stream());
+  return dw;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "machin_amd gfx950 HIP kernels";
   m.def("sumtree_update", &sumtree_update);
@@ -1745,4 +1792,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_igemm_fits", &conv_igemm_fits);
   m.def("conv_igemm_fwd", &conv_igemm_fwd);
   m.def("conv_igemm_bwd_data", &conv_igemm_bwd_data);
+  m.def("conv_igemm_wrw_fits", &conv_igemm_wrw_fits);
+  m.def("conv_igemm_wrw", &conv_igemm_wrw);
 }

@@ -74,6 +74,7 @@
 // and a window never leaves its sample's resident image (forward:
 // (OH-1) S + KH <= H; data gradient: a + T - 1 <= ceil(H/S) + T - 2).
 #include "common.h"
+#include "conv_igemm.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -287,7 +288,7 @@ static int cig_cu_count() {
 
 // 64 KB of LDS per workgroup: two resident workgroups per CU, and the
 // grid is that many. MACHIN_CONV_IGEMM_WG overrides it (read per call).
-static unsigned cig_grid(int64_t groups) {
+unsigned cig_grid(int64_t groups) {
   int64_t grid = (int64_t)cig_cu_count() * 2;
   if (const char* e = getenv("MACHIN_CONV_IGEMM_WG")) grid = atol(e);
   if (grid < 1) grid = 1;
@@ -295,14 +296,7 @@ static unsigned cig_grid(int64_t groups) {
   return (unsigned)grid;
 }
 
-// The geometry table: the two Nature layers. The lookup, the group
-// size and the kernels' template arguments are all read from it.
-struct cig_geom { int ksize, stride, cin, cout; };
-#define CIG_NGEOM 2
-static constexpr cig_geom CIG_GEOM[CIG_NGEOM] = {{4, 2, 32, 64},
-                                                 {3, 1, 64, 64}};
-
-// Index of the layer in the table, -1 for anything else.
+// Index of the layer in the table (conv_igemm.h), -1 for anything else.
 int conv_igemm_geometry(int64_t cin, int64_t cout, int64_t ksize,
                         int64_t stride) {
   for (int i = 0; i < CIG_NGEOM; ++i) {

@@ -38,6 +38,7 @@ SOURCES = [
     "conv1_wrw.hip",
     "bias_act.hip",
     "conv_igemm.hip",
+    "conv_igemm_wrw.hip",
 ]
 # Per-source flags. quantile_loss.hip is scalar fp32 VALU code whose sums
 # have a fixed order; it is compiled without the packed fp32 instructions
@@ -107,7 +108,8 @@ class BuildHipExt(Command):
             obj = os.path.join(
                 obj_dir, os.path.splitext(src_name)[0] + ".o"
             )
-            deps = [src, os.path.join(HIP_DIR, "common.h"), __file__]
+            deps = [src, os.path.join(HIP_DIR, "common.h"),
+                    os.path.join(HIP_DIR, "conv_igemm.h"), __file__]
             if os.path.exists(obj) and all(
                 os.path.getmtime(obj) >= os.path.getmtime(d)
                 for d in deps
