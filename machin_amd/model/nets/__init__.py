@@ -3,6 +3,7 @@ from .base import (
     dynamic_module_wrapper,
     static_module_wrapper,
 )
+from .fused_mlp import FusedMLP
 from .gaussian import GaussianPolicyHead
 from .iqn import CosineTauEmbedding, ImplicitQuantileHead
 from .nature_cnn import ActorCriticCNN, NatureCNN, mlp
@@ -22,6 +23,7 @@ __all__ = [
     "NatureCNN",
     "ActorCriticCNN",
     "mlp",
+    "FusedMLP",
     "ResNet",
     "GaussianPolicyHead",
     "NoisyLinear",

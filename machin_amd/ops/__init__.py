@@ -1223,6 +1223,148 @@ def iqn_embedding(psi: t.Tensor, taus: t.Tensor, weight: t.Tensor,
     return _IQNEmbedding.apply(psi, taus.detach(), weight, bias)
 
 
+# ======================================================================
+# whole-network fused MLP (state-vector nets, twin critics, sub-policies)
+# ======================================================================
+FUSED_MLP_MAX_LAYERS = 4
+FUSED_MLP_MAX_WIDTH = 256
+# Device tensors with more rows than this take the torch form. Set from
+# the measured table in docs/PERFORMANCE.md ("Fused MLP").
+FUSED_MLP_MAX_BATCH = 4096
+
+
+def _fused_mlp_check(x, weights, biases):
+    """Shared argument validation of :func:`fused_mlp`; returns
+    ``(E, B, shared)`` with ``E = None`` without an ensemble."""
+    weights, biases = list(weights), list(biases)
+    L = len(weights)
+    if not 2 <= L <= FUSED_MLP_MAX_LAYERS or len(biases) != L:
+        raise ValueError(
+            f"need 2 to {FUSED_MLP_MAX_LAYERS} layers, a bias for each"
+        )
+    ens = weights[0].dim() == 3
+    E = weights[0].shape[0] if ens else None
+    lead = (E,) if ens else ()
+    if x.dim() not in (2, 3) or (x.dim() == 3 and not ens) or x.numel() == 0:
+        raise ValueError("x must be [B, K] or, with an ensemble, [E, B, K]")
+    if x.dim() == 3 and x.shape[0] != E:
+        raise ValueError(f"x must have {E} members")
+    width = x.shape[-1]
+    for name, p in [("x", x)] + [("weight", w) for w in weights] \
+            + [("bias", b) for b in biases]:
+        if p.dtype != t.float32:
+            raise ValueError(f"{name} must be float32")
+        if p.device != x.device:
+            raise ValueError(f"{name} must be on x's device")
+    for w, b in zip(weights, biases):
+        if not 1 <= width <= FUSED_MLP_MAX_WIDTH:
+            raise ValueError(
+                f"every width must be in [1, {FUSED_MLP_MAX_WIDTH}]")
+        if w.dim() != len(lead) + 2 or tuple(w.shape[:-2]) != lead \
+                or w.shape[-1] != width:
+            raise ValueError(f"a weight must be {lead + ('N', width)}")
+        width = w.shape[-2]
+        if tuple(b.shape) != lead + (width,):
+            raise ValueError(f"a bias must be {lead + (width,)}")
+    if not 1 <= width <= FUSED_MLP_MAX_WIDTH:
+        raise ValueError(f"every width must be in [1, {FUSED_MLP_MAX_WIDTH}]")
+    return E, x.shape[-2], ens and x.dim() == 2
+
+
+def _fused_mlp_torch(x, weights, biases):
+    """Torch composition of :func:`fused_mlp` (the CPU path, the path
+    above ``FUSED_MLP_MAX_BATCH`` and the form the kernels are tested and
+    timed against): ``addmm`` / ``baddbmm`` and ``relu``."""
+    E, B, shared = _fused_mlp_check(x, weights, biases)
+    a = x
+    if shared:
+        a = x.unsqueeze(0).expand(E, *x.shape)
+    last = len(weights) - 1
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        if E is None:
+            a = t.addmm(b, a, w.t())
+        else:
+            a = t.baddbmm(b.unsqueeze(1), a, w.transpose(1, 2))
+        if l < last:
+            a = t.relu(a)
+    return a
+
+
+class _FusedMLP(t.autograd.Function):
+    """``apply(x, L, *weights, *biases)`` on contiguous fp32 device
+    tensors in ensemble form: ``x`` is ``[E, B, K_0]``, or ``[B, K_0]``
+    when the members share it."""
+
+    @staticmethod
+    def forward(ctx, x, L, *params):
+        weights, biases = list(params[:L]), list(params[L:])
+        needs = ctx.needs_input_grad
+        save = any(needs)
+        y, *saved = _require_ext().fused_mlp_fwd(x, weights, biases, save)
+        ctx.L = L
+        ctx.save_for_backward(x, *weights, *saved)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = ctx.L
+        x, *rest = ctx.saved_tensors
+        weights, saved = rest[:L], rest[L:]
+        needs = ctx.needs_input_grad
+        mask = 0
+        for l in range(L):
+            if needs[2 + l] or needs[2 + L + l]:
+                mask |= 1 << l
+        out = _require_ext().fused_mlp_bwd(
+            dy.contiguous(), x, weights, saved, needs[0], mask
+        )
+        grads = [g if need else None for g, need in zip(out[1:], needs[2:])]
+        return (out[0], None, *grads)
+
+
+def fused_mlp(x: t.Tensor, weights, biases) -> t.Tensor:
+    """A whole MLP of ``L`` linear layers (``2 <= L <=
+    FUSED_MLP_MAX_LAYERS``) with ReLU after every layer but the last::
+
+        a_0 = x,  a_l = relu(a_{l-1} @ weights[l-1].T + biases[l-1]),
+        y = a_{L-1} @ weights[L-1].T + biases[L-1]
+
+    ``weights[l]`` is ``[K_{l+1}, K_l]`` (the ``nn.Linear`` layout),
+    ``biases[l]`` ``[K_{l+1}]`` and ``x`` ``[B, K_0]``; ``y`` is
+    ``[B, K_L]``. With an ensemble of ``E`` independent networks of one
+    shape (twin critics, MADDPG sub-policies) the parameters carry a
+    leading ``E``; ``x`` is ``[E, B, K_0]``, or ``[B, K_0]`` shared by
+    all members, and ``y`` is ``[E, B, K_L]``. Every width is in
+    ``[1, FUSED_MLP_MAX_WIDTH]``; everything is contiguous fp32
+    (anything else raises ``ValueError``).
+
+    Differentiable in ``x``, every weight and every bias, each gradient
+    computed only where ``requires_grad`` asks for it. ReLU passes no
+    gradient at a pre-activation of exactly 0, as in torch.
+
+    On ROCm this is one gfx950 kernel forward (activations stay in LDS
+    from the first layer to the last, weights stream from L2), one for
+    the data path of the backward and one for every layer's weight and
+    bias gradient (machin_amd/ops/hip/fused_mlp.hip), on the fp32 matrix
+    instruction. No atomics: results are reproducible bit for bit. CPU
+    tensors, and device tensors with ``B > FUSED_MLP_MAX_BATCH``, take
+    the same semantics as a torch composition.
+    """
+    weights, biases = list(weights), list(biases)
+    E, B, _ = _fused_mlp_check(x, weights, biases)
+    if not x.is_cuda or B > FUSED_MLP_MAX_BATCH:
+        return _fused_mlp_torch(x, weights, biases)
+    if E is None:
+        x = x.unsqueeze(0)
+        weights = [w.unsqueeze(0) for w in weights]
+        biases = [b.unsqueeze(0) for b in biases]
+    y = _FusedMLP.apply(
+        x.contiguous(), len(weights), *[w.contiguous() for w in weights],
+        *[b.contiguous() for b in biases]
+    )
+    return y if E is not None else y.squeeze(0)
+
+
 def _factorised_noise_torch(buf: t.Tensor, seed: int, offset: int):
     gen = t.Generator(device="cpu")
     gen.manual_seed(
@@ -2122,6 +2264,7 @@ __all__ = [
     "quantile_huber_loss",
     "noisy_linear",
     "iqn_embedding",
+    "fused_mlp",
     "factorised_noise_",
     "FusedPolyak",
     "FusedRMSprop",

@@ -169,6 +169,16 @@ void iqn_embed_bwd_launch(const void*, const void*, const float*,
                           hipStream_t);
 int iqn_embed_bwd_slices(int64_t, int64_t, int*);
 
+void fused_mlp_fwd_launch(const float*, int64_t, const float* const*,
+                          const float* const*, float* const*, float*,
+                          const int*, int, int, int, bool, hipStream_t);
+void fused_mlp_bwd_data_launch(const float*, const float* const*,
+                               float* const*, float* const*, float*, float*,
+                               const int*, int, int, int, int, hipStream_t);
+void fused_mlp_bwd_param_launch(const float* const*, const float* const*,
+                                int64_t, float* const*, float* const*,
+                                const int*, int, int, int, int, hipStream_t);
+
 namespace {
 
 void check_f32_cuda(const Tensor& t, const char* name) {
@@ -633,6 +643,141 @@ std::vector<Tensor> iqn_embed_bwd(Tensor g, Tensor psi, Tensor taus,
                        (int)D, (int)K, per, S,
                        psi.scalar_type() == at::kBFloat16, current_stream());
   return {dpsi, dweight, dbias};
+}
+
+// ------------------------------------------------------------------
+// whole-network fused MLP (semantics: machin_amd.ops.fused_mlp)
+// ------------------------------------------------------------------
+constexpr int kFusedMlpMaxLayers = 4;
+constexpr int64_t kFusedMlpMaxWidth = 256;
+
+// x [E, B, K_0], or [B, K_0] shared by the members; weights[l]
+// [E, K_{l+1}, K_l]. Fills k[0 .. L] and returns {E, B}.
+std::pair<int64_t, int64_t> check_fused_mlp(
+    const Tensor& x, const std::vector<Tensor>& weights, int* k) {
+  const int64_t L = (int64_t)weights.size();
+  TORCH_CHECK(L >= 2 && L <= kFusedMlpMaxLayers, "need 2 to ",
+              kFusedMlpMaxLayers, " layers");
+  check_f32_cuda(x, "x");
+  TORCH_CHECK(x.dim() == 2 || x.dim() == 3, "x must be [B, K] or [E, B, K]");
+  TORCH_CHECK(weights[0].dim() == 3, "weights must be [E, N, K]");
+  const int64_t E = weights[0].size(0), B = x.size(-2);
+  TORCH_CHECK(x.dim() == 2 || x.size(0) == E, "x must have E members");
+  TORCH_CHECK(E >= 1 && E < 65536 && B >= 1 &&
+                  E * B * kFusedMlpMaxWidth < ((int64_t)1 << 31),
+              "need 1 <= E < 65536, B >= 1 and E * B < 2^23");
+  int64_t width = x.size(-1);
+  for (int64_t l = 0; l < L; ++l) {
+    const Tensor& w = weights[l];
+    TORCH_CHECK(width >= 1 && width <= kFusedMlpMaxWidth,
+                "every width must be in [1, ", kFusedMlpMaxWidth, "]");
+    TORCH_CHECK(w.dim() == 3 && w.size(0) == E && w.size(2) == width,
+                "weights[", l, "] must be [", E, ", N, ", width, "]");
+    k[l] = (int)width;
+    check_arg(w, x, at::kFloat, E * w.size(1) * width, "weight");
+    width = w.size(1);
+  }
+  TORCH_CHECK(width >= 1 && width <= kFusedMlpMaxWidth,
+              "every width must be in [1, ", kFusedMlpMaxWidth, "]");
+  k[L] = (int)width;
+  return {E, B};
+}
+
+// Returns {y [E, B, K_L]} and, when save, the post-ReLU activations
+// a_1 .. a_{L-1} ([E, B, K_l] each) after it.
+std::vector<Tensor> fused_mlp_fwd(Tensor x, std::vector<Tensor> weights,
+                                  std::vector<Tensor> biases, bool save) {
+  int k[kFusedMlpMaxLayers + 1];
+  const auto [E, B] = check_fused_mlp(x, weights, k);
+  const int L = (int)weights.size();
+  TORCH_CHECK((int)biases.size() == L, "need one bias per layer");
+  const float *w[kFusedMlpMaxLayers], *b[kFusedMlpMaxLayers];
+  float* sav[kFusedMlpMaxLayers] = {};
+  for (int l = 0; l < L; ++l) {
+    TORCH_CHECK(biases[l].dim() == 2 && biases[l].size(0) == E,
+                "biases must be [E, N]");
+    check_arg(biases[l], x, at::kFloat, E * k[l + 1], "bias");
+    w[l] = weights[l].data_ptr<float>();
+    b[l] = biases[l].data_ptr<float>();
+  }
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  std::vector<Tensor> out{at::empty({E, B, k[L]}, x.options())};
+  for (int l = 0; save && l < L - 1; ++l) {
+    out.push_back(at::empty({E, B, k[l + 1]}, x.options()));
+    sav[l] = out.back().data_ptr<float>();
+  }
+  fused_mlp_fwd_launch(x.data_ptr<float>(),
+                       x.dim() == 2 ? 0 : B * (int64_t)k[0], w, b, sav,
+                       out[0].data_ptr<float>(), k, L, (int)B, (int)E, save,
+                       current_stream());
+  return out;
+}
+
+// saved: what fused_mlp_fwd returned after y. Bit l of mask asks for
+// dW_l and db_l. Returns {dx, dW_0 .., db_0 ..}; tensors that were not
+// asked for are undefined (None).
+std::vector<Tensor> fused_mlp_bwd(Tensor dy, Tensor x,
+                                  std::vector<Tensor> weights,
+                                  std::vector<Tensor> saved, bool need_dx,
+                                  int64_t mask) {
+  int k[kFusedMlpMaxLayers + 1];
+  const auto [E, B] = check_fused_mlp(x, weights, k);
+  const int L = (int)weights.size();
+  TORCH_CHECK((int)saved.size() == L - 1, "need L - 1 saved activations");
+  TORCH_CHECK(mask >= 0 && mask < (1 << L), "mask names a missing layer");
+  TORCH_CHECK(dy.dim() == 3, "dy must be [E, B, N]");
+  check_arg(dy, x, at::kFloat, E * B * k[L], "dy");
+  const bool shared = x.dim() == 2;
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  const float *w[kFusedMlpMaxLayers], *dzs[kFusedMlpMaxLayers],
+      *acts[kFusedMlpMaxLayers];
+  float *sav[kFusedMlpMaxLayers] = {}, *dz[kFusedMlpMaxLayers] = {},
+        *dw[kFusedMlpMaxLayers] = {}, *db[kFusedMlpMaxLayers] = {};
+  // the lowest layer (1-based) whose dz is wanted; 0: dx
+  int lo = L;
+  for (int l = L - 1; l >= 0; --l)
+    if ((mask >> l) & 1) lo = l + 1;
+  if (need_dx) lo = 0;
+  std::vector<Tensor> out(1 + 2 * L), keep;
+  acts[0] = x.data_ptr<float>();
+  for (int l = 0; l < L; ++l) {
+    w[l] = weights[l].data_ptr<float>();
+    if (l < L - 1) {
+      check_arg(saved[l], x, at::kFloat, E * B * k[l + 1], "saved");
+      sav[l] = saved[l].data_ptr<float>();
+      acts[l + 1] = sav[l];
+      if (l + 1 >= lo) {
+        keep.push_back(at::empty({E, B, k[l + 1]}, x.options()));
+        dz[l] = keep.back().data_ptr<float>();
+      }
+      dzs[l] = dz[l];
+    } else {
+      dzs[l] = dy.data_ptr<float>();
+    }
+    if ((mask >> l) & 1) {
+      out[1 + l] = at::empty({E, k[l + 1], k[l]}, x.options());
+      out[1 + L + l] = at::empty({E, k[l + 1]}, x.options());
+      dw[l] = out[1 + l].data_ptr<float>();
+      db[l] = out[1 + L + l].data_ptr<float>();
+    }
+  }
+  float *dx_members = nullptr, *dx = nullptr;
+  if (need_dx) {
+    Tensor members = at::empty({E, B, k[0]}, x.options());
+    dx_members = members.data_ptr<float>();
+    out[0] = members;
+    if (shared) {
+      out[0] = at::empty({B, k[0]}, x.options());
+      dx = out[0].data_ptr<float>();
+      keep.push_back(members);
+    }
+  }
+  fused_mlp_bwd_data_launch(dy.data_ptr<float>(), w, sav, dz, dx_members, dx,
+                            k, L, (int)B, (int)E, lo, current_stream());
+  fused_mlp_bwd_param_launch(dzs, acts, shared ? 0 : B * (int64_t)k[0], dw,
+                             db, k, L, (int)B, (int)E, (int)mask,
+                             current_stream());
+  return out;
 }
 
 void factorised_noise_(Tensor buf, int64_t seed, int64_t offset) {
@@ -1759,6 +1904,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("noisy_linear_mfma_bwd_weight", &noisy_linear_mfma_bwd_weight);
   m.def("iqn_embed_fwd", &iqn_embed_fwd);
   m.def("iqn_embed_bwd", &iqn_embed_bwd);
+  m.def("fused_mlp_fwd", &fused_mlp_fwd);
+  m.def("fused_mlp_bwd", &fused_mlp_bwd);
   m.def("multi_tensor_polyak", &multi_tensor_polyak);
   m.def("multi_tensor_polyak_cached", &multi_tensor_polyak_cached);
   m.def("fused_rmsprop_cached", &fused_rmsprop_cached);

@@ -29,6 +29,7 @@ SOURCES = [
     "noisy_linear.hip",
     "noisy_linear_mfma.hip",
     "iqn_embed.hip",
+    "fused_mlp.hip",
     "multi_tensor.hip",
     "distributions.hip",
     "elementwise.hip",
